@@ -9,6 +9,16 @@ weights; no network/datasets in this environment), teacher-forced T=20.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
                     [--cnn vgg16|resnet50] [--no-hip-graph]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warmup
+steps, K timed steps, one JSON line.  --dump-outputs DIR additionally
+writes what the last timed train_step returned (the loss dict and the
+attention map) plus a seeded sample of the updated trainable weights as
+DIR/<name>.npy (float32), so two builds can be compared output for output;
+inputs and initial weights are seeded, hence identical from run to run.
+--full is reserved for measurements beyond the headline figure (there are
+none at present, so it changes nothing).
 
 For N>1 the driver launches this under torch.distributed.run with one rank
 per GPU (RCCL over xGMI); per-GPU work is fixed (weak scaling).  Timing: W
@@ -49,6 +59,28 @@ def make_batches(cfg, device, n_batches=4):
     return batches
 
 
+PARAM_SAMPLE = 1 << 20  # elements of the updated weights kept in a dump
+
+
+def dump_outputs(out_dir, out, model, seed):
+    """Write the last timed train_step's return value (every entry of its
+    dict) and a fixed seeded sample of the updated trainable weights as
+    float32 .npy files; a few MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        a = v.detach().float().cpu().numpy() if torch.is_tensor(v) \
+            else np.asarray(v, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + '.npy'),
+                np.ascontiguousarray(a, dtype=np.float32))
+    flat = torch.cat([p.detach().float().reshape(-1).cpu()
+                      for p in model.model.parameters() if p.requires_grad])
+    if flat.numel() > PARAM_SAMPLE:
+        g = torch.Generator(device='cpu').manual_seed(seed)
+        idx = torch.randperm(flat.numel(), generator=g)[:PARAM_SAMPLE]
+        flat = flat[idx.sort().values]
+    np.save(os.path.join(out_dir, 'params_sample.npy'), flat.numpy())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--gpus', type=int, default=1)
@@ -60,6 +92,11 @@ def main():
     p.add_argument('--train-cnn', action='store_true',
                    help='BASELINE config #4 shape: end-to-end CNN+RNN')
     p.add_argument('--no-hip-graph', action='store_true')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the last timed step\'s outputs as DIR/*.npy')
+    p.add_argument('--full', action='store_true',
+                   help='also run every measurement beyond the headline '
+                        'figure (none at present)')
     args = p.parse_args()
 
     from config import Config
@@ -98,10 +135,14 @@ def main():
 
     sync()
     t0 = time.perf_counter()
+    out = None
     for i in range(args.steps):
-        model.train_step(*batches[i % len(batches)])
+        out = model.train_step(*batches[i % len(batches)])
     sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and out is not None and rank == 0:
+        dump_outputs(args.dump_outputs, out, model, cfg.seed)
 
     # max over ranks
     if dist is not None:

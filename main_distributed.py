@@ -26,7 +26,10 @@ from sat_amd.parallel.launch import init_distributed, shard_dataset
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    rank, world, local_rank = init_distributed()
+    # --device cpu means gloo ranks even on a box that has a GPU (nccl
+    # would bind rank r to GPU r, which need not exist)
+    rank, world, local_rank = init_distributed(
+        'gloo' if args.device == 'cpu' else None)
 
     config = Config()
     config.phase = args.phase

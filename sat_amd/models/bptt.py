@@ -369,7 +369,8 @@ class DecodeHeadBPTT(torch.autograd.Function):
         # tiled kernel: hipBLASLt ran this [V,TB]x[TB,Dd] shape at
         # 43 TF / 152 us (r02e profile); two small transposes + the
         # MFMA tile land at ~25 us.
-        if fast_dx:
+        # (here K is T·B: odd batches, e.g. B=1, take the matmul too)
+        if fast_dx and DL.shape[0] % 8 == 0:
             dWd2 = _C.dense_fwd(DL.t().contiguous(),
                                 HD.t().contiguous(), eb, 0).float()
         else:

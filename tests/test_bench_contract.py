@@ -29,6 +29,37 @@ def test_bench_json_contract():
             'parallelism'} <= set(d['config'])
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float .npy
+    files (64 MB at most); --full is accepted and keeps the result line."""
+    import numpy as np
+    out_dir = tmp_path / 'dump'
+    r = subprocess.run(
+        [sys.executable, 'bench.py', '--gpus', '1', '--steps', '2',
+         '--warmup', '0', '--batch', '1', '--full',
+         '--dump-outputs', str(out_dir)],
+        capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d['metric'] == 'training images/sec'
+    assert d['steps'] == 2
+    assert d['ms_per_step'] > 0
+    assert abs(d['value'] - 1000.0 / d['ms_per_step']) \
+        <= 0.01 * d['value']  # batch 1: images/sec == steps/sec
+    files = sorted(os.listdir(out_dir))
+    assert {'total_loss.npy', 'accuracy.npy', 'attentions.npy',
+            'params_sample.npy'} <= set(files)
+    total = 0
+    for f in files:
+        a = np.load(out_dir / f)
+        assert a.dtype in (np.float32, np.float64), f
+        assert np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    assert np.load(out_dir / 'attentions.npy').shape == (1, 196)
+    assert float(np.load(out_dir / 'total_loss.npy').reshape(-1)[0]) > 0
+
+
 def test_graft_entry_has_build_and_smoke():
     import importlib.util
     spec = importlib.util.spec_from_file_location(

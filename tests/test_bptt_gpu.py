@@ -68,6 +68,24 @@ def test_bptt_matches_per_op_path(tiny_config):
     assert set(grads_a) == set(grads_b)
     for n in grads_a:
         ga, gb = grads_a[n], grads_b[n]
+        if n == 'decoder.att_fc_1b.bias':
+            # With dropout off the attention logits are
+            # v·(tanh(fc_1a) + tanh(fc_1b)): fc_1b shifts all L logits of
+            # a row by one constant, softmax ignores the shift, so the
+            # exact data gradient of fc_1b is ZERO (its weight keeps the
+            # L2 term and is compared like the rest; the bias has none).
+            # For the bias both paths return only the
+            # rounding residue of L·T·B ~ 1.1e4 cancelling fp32 terms
+            # (accumulated with atomics, so it differs run to run; seen
+            # 1e-10..1e-9) and a relative comparison of two residues is
+            # noise.  Instead both must vanish against fc_1a's gradient,
+            # which sums the same terms without the cancellation: worst
+            # case 1.1e4 * 2^-24 = 6.6e-4 of it, one decade of margin.
+            scale = grads_b[n.replace('att_fc_1b', 'att_fc_1a')].abs().max()
+            assert scale > 0
+            for g in (ga, gb):
+                assert (g.abs().max() / scale).item() < 1e-2, n
+            continue
         denom = gb.abs().max().clamp_min(1e-8)
         rel = ((ga - gb).abs().max() / denom).item()
         assert rel < 8e-2, (n, rel)
