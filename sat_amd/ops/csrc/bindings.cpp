@@ -51,11 +51,6 @@ at::Tensor conv_igemm_glds_fwd(at::Tensor padded, at::Tensor w_ohwi,
 std::vector<at::Tensor> dense_lstm_fwd(at::Tensor xh, at::Tensor wl,
                                        at::Tensor bl, at::Tensor c_prev,
                                        double fb);
-void dense_drop_fwd(at::Tensor x, at::Tensor w, at::Tensor b, int64_t act,
-                    at::Tensor seed, double p, int64_t salt,
-                    at::Tensor y, at::Tensor ydrop);
-at::Tensor dense_fwd_out(at::Tensor x, at::Tensor w, at::Tensor bias,
-                         int64_t act, at::Tensor out);
 std::vector<at::Tensor> lstm_pointwise_bwd_out(at::Tensor gates,
                                                at::Tensor c, at::Tensor dh,
                                                at::Tensor dc, double fb,
@@ -158,10 +153,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("conv3x3_wgrad", &conv3x3_wgrad,
           "3x3 conv weight grad: transpose-staged MFMA split-K reduce");
     m.def("dense_lstm_fwd", &dense_lstm_fwd);
-    m.def("dense_drop_fwd", &dense_drop_fwd);
     m.def("conv3_fwd", &conv3_fwd,
           "direct NHWC conv for 3-channel 3x3/s1 (VGG conv1_1)");
-    m.def("dense_fwd_out", &dense_fwd_out);
     m.def("lstm_pointwise_bwd_out", &lstm_pointwise_bwd_out);
     m.def("lstm_in_fuse", &lstm_in_fuse);
     m.def("expand_fuse", &expand_fuse);

@@ -1,28 +1,11 @@
 // Per-step pointwise chain fusions for the hand-written BPTT
 // (sat_amd/models/bptt.py).  Each kernel replaces a 4-8 launch eager chain
 // (cat / slice / dropout / add) with one launch writing straight into the
-// step-major batched buffers.  Dropout masks use the same counter hash as
-// kernels.hip (seed value hoisted once per kernel), with flat per-tensor
+// step-major batched buffers.  Dropout masks use the counter hash of
+// common.h (seed value hoisted once per kernel), with flat per-tensor
 // indices identical to the standalone hash_dropout calls they replace.
 
 #include "common.h"
-
-__device__ __forceinline__ uint32_t mix3b(uint32_t a, uint32_t b,
-                                          uint32_t c) {
-    uint32_t h = a * 0x9E3779B1u ^ b * 0x85EBCA77u ^ c * 0xC2B2AE3Du;
-    h ^= h >> 16; h *= 0x7FEB352Du;
-    h ^= h >> 15; h *= 0x846CA68Bu;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ float dscale(uint32_t seed, int salt,
-                                        uint32_t idx, float p) {
-    if (p <= 0.f) return 1.f;
-    uint32_t h = mix3b(seed, (uint32_t)salt, idx);
-    float u = (h >> 8) * (1.0f / 16777216.0f);
-    return u >= p ? 1.0f / (1.0f - p) : 0.0f;
-}
 
 // ---- forward: xh = [dropout(cat(pooled, emb), p_lstm, salt), state_h] ----
 
@@ -44,7 +27,7 @@ __global__ void lstm_in_fuse_kernel(const bf16* __restrict__ pooled,
     if (j < I) {
         val = (j < D) ? bf2f(pooled[(int64_t)b * D + j])
                       : bf2f(table[ids[b] * E + (j - D)]);
-        val *= dscale(seed, salt, (uint32_t)(b * I + j), p);
+        val *= drop_scale(seed, salt, (uint32_t)(b * I + j), p);
     } else {
         val = bf2f(sth[(int64_t)b * H + (j - I)]);
     }
@@ -93,21 +76,21 @@ __global__ void expand_fuse_kernel(const bf16* __restrict__ h_raw,
     if (j < H) {
         float h = bf2f(h_raw[(int64_t)b * H + j]);
         uint32_t hidx = (uint32_t)(b * H + j);
-        float ot = h * dscale(seed, s + 4, hidx, p_lstm);
+        float ot = h * drop_scale(seed, s + 4, hidx, p_lstm);
         out_t[(int64_t)b * H + j] = f2bf(ot);
         sth_t[(int64_t)b * H + j] =
-            f2bf(h * dscale(seed, s + 5, hidx, p_lstm));
+            f2bf(h * drop_scale(seed, s + 5, hidx, p_lstm));
         if (od_next != nullptr)
             od_next[(int64_t)b * H + j] =
-                f2bf(ot * dscale(seed, s + 16 + 1, hidx, p_fc));
+                f2bf(ot * drop_scale(seed, s + 16 + 1, hidx, p_fc));
         val = ot;
     } else if (j < H + D) {
         val = bf2f(pooled[(int64_t)b * D + (j - H)]);
     } else {
         val = bf2f(table[ids[b] * E + (j - H - D)]);
     }
-    expdrop[idx] = f2bf(val * dscale(seed, s + 6, (uint32_t)(b * W + j),
-                                     p_fc));
+    expdrop[idx] = f2bf(val * drop_scale(seed, s + 6,
+                                         (uint32_t)(b * W + j), p_fc));
 }
 
 std::vector<at::Tensor> expand_fuse(at::Tensor h_raw, at::Tensor pooled,
@@ -156,13 +139,13 @@ __global__ void dexp_fuse_kernel(const bf16* __restrict__ dexpd,
     if (idx >= (int64_t)B * W) return;
     int b = idx / W, j = idx % W;
     float dexp = bf2f(dexpd[idx])
-        * dscale(seed, s + 6, (uint32_t)(b * W + j), p_fc);
+        * drop_scale(seed, s + 6, (uint32_t)(b * W + j), p_fc);
     if (j < H) {
         uint32_t hidx = (uint32_t)(b * H + j);
         float dout = dexp + bf2f(d_out_carry[(int64_t)b * H + j]);
-        float dh = dout * dscale(seed, s + 4, hidx, p_lstm)
+        float dh = dout * drop_scale(seed, s + 4, hidx, p_lstm)
             + bf2f(d_sth_carry[(int64_t)b * H + j])
-            * dscale(seed, s + 5, hidx, p_lstm);
+            * drop_scale(seed, s + 5, hidx, p_lstm);
         dh_raw[(int64_t)b * H + j] = f2bf(dh);
     } else if (j < H + D) {
         dpool_dec[(int64_t)b * D + (j - H)] = f2bf(dexp);
@@ -213,7 +196,7 @@ __global__ void dx_fuse_kernel(const bf16* __restrict__ dxh,
     int b = idx / W, j = idx % W;
     float g = bf2f(dxh[idx]);
     if (j < I) {
-        g *= dscale(seed, salt, (uint32_t)(b * I + j), p);
+        g *= drop_scale(seed, salt, (uint32_t)(b * I + j), p);
         if (j < D)
             dpooled[(int64_t)b * D + j] =
                 f2bf(g + bf2f(dpool_dec[(int64_t)b * D + j]));
@@ -257,7 +240,8 @@ __global__ void hash_dropout_out_kernel(const bf16* __restrict__ x,
     const uint32_t seed = (uint32_t)(*seed_p);
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    y[idx] = f2bf(bf2f(x[idx]) * dscale(seed, salt, (uint32_t)idx, p));
+    y[idx] = f2bf(bf2f(x[idx])
+                  * drop_scale(seed, salt, (uint32_t)idx, p));
 }
 
 void hash_dropout_out(at::Tensor x, at::Tensor seed, double p,
@@ -294,8 +278,8 @@ __global__ void hash_dropout_steps_kernel(const bf16* __restrict__ x,
         bf16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-            o[e] = f2bf(bf2f(v[e]) * dscale(seed, salt,
-                                            (uint32_t)(j + e), p));
+            o[e] = f2bf(bf2f(v[e]) * drop_scale(seed, salt,
+                                                (uint32_t)(j + e), p));
         *(bf16x8*)(y + i8) = o;
     }
 }
@@ -390,7 +374,8 @@ __global__ void hash_dropout_slabs_kernel(const bf16* __restrict__ x,
     bf16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-        o[e] = f2bf(bf2f(v[e]) * dscale(seed, salt, (uint32_t)(j + e), p));
+        o[e] = f2bf(bf2f(v[e])
+                    * drop_scale(seed, salt, (uint32_t)(j + e), p));
     *(bf16x8*)(y + i8) = o;
 }
 
@@ -437,30 +422,24 @@ __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
     if (idx >= (int64_t)B * W) return;
     int b = idx / W, j = idx % W;
     float dexp = bf2f(dexpd[idx])
-        * dscale(seed, s + 6, (uint32_t)(b * W + j), p_fc);
+        * drop_scale(seed, s + 6, (uint32_t)(b * W + j), p_fc);
     if (j < H) {
         uint32_t hidx = (uint32_t)(b * H + j);
         float dout = dexp + bf2f(d_out_carry[(int64_t)b * H + j]);
-        float dhv = dout * dscale(seed, s + 4, hidx, p_lstm)
+        float dhv = dout * drop_scale(seed, s + 4, hidx, p_lstm)
             + bf2f(d_sth_carry[(int64_t)b * H + j])
-            * dscale(seed, s + 5, hidx, p_lstm);
-        // LSTM pointwise backward (same math as lstm_pw_bwd_kernel)
-        const bf16* g = gates + (int64_t)b * 4 * H;
-        float gi = 1.f / (1.f + __expf(-bf2f(g[j])));
-        float gj = tanhf(bf2f(g[H + j]));
-        float gf = 1.f / (1.f + __expf(-(bf2f(g[2 * H + j]) + fb)));
-        float go = 1.f / (1.f + __expf(-bf2f(g[3 * H + j])));
-        float cp = bf2f(c[(int64_t)b * H + j]);
-        float cn = cp * gf + gi * gj;
-        float tc = tanhf(cn);
+            * drop_scale(seed, s + 5, hidx, p_lstm);
+        const bf16* gp = gates + (int64_t)b * 4 * H + j;
+        float g[4], dg[4], dcp;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = bf2f(gp[q * H]);
         float dcv = (dc != nullptr) ? bf2f(dc[(int64_t)b * H + j]) : 0.f;
-        float dct = dcv + dhv * go * (1.f - tc * tc);
-        bf16* dg = dgates + (int64_t)b * 4 * H;
-        dg[j]         = f2bf(dct * gj * gi * (1.f - gi));
-        dg[H + j]     = f2bf(dct * gi * (1.f - gj * gj));
-        dg[2 * H + j] = f2bf(dct * cp * gf * (1.f - gf));
-        dg[3 * H + j] = f2bf(dhv * tc * go * (1.f - go));
-        dc_prev[(int64_t)b * H + j] = f2bf(dct * gf);
+        lstm_cell_bwd(g, bf2f(c[(int64_t)b * H + j]), dhv, dcv, fb, dg,
+                      dcp);
+        bf16* dgp = dgates + (int64_t)b * 4 * H + j;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dgp[q * H] = f2bf(dg[q]);
+        dc_prev[(int64_t)b * H + j] = f2bf(dcp);
     } else if (j < H + D) {
         dpool_dec[(int64_t)b * D + (j - H)] = f2bf(dexp);
     } else {

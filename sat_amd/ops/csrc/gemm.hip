@@ -8,11 +8,13 @@
 //     projection [B·196,512]x[512,512]);
 //   * tiled_gemm<4,1,2,4>  — 128x64 tile for N <= 512: twice the blocks,
 //     fills the 256-CU / 8-XCD chip at the flagship shapes;
-//   * skinny split-K       — M <= 32 (decode/LSTM GEMMs at batch 32):
-//     one 32-row tile, 16-column wave slabs, K split across blocks with
-//     fp32 atomic accumulation + a fused bias/act epilogue pass.  The
-//     128x128 kernel runs these shapes at 8-40 blocks (latency-bound,
-//     measured 40-60us each); the skinny kernel runs 128-316 blocks.
+//   * skinny split-K       — M <= 128 (decode/LSTM GEMMs at per-GPU
+//     batch 32..128): one RF*16-row tile (RF = 2/4/8), 16-column wave
+//     slabs, K split across blocks into per-split fp32 slabs that a
+//     separate epilogue kernel sums and finishes (bias/act, dropout,
+//     LSTM gate math, dx scatter).  The 128x128 kernel runs these
+//     shapes at 8-40 blocks (latency-bound, measured 40-60us each); the
+//     skinny kernel runs 128-316 blocks.
 //
 // CDNA4 structure per the gfx950 playbook: v_mfma_f32_16x16x32_bf16,
 // fp32 AGPR accumulation, LDS staging with +8 bf16 row padding (bank
@@ -21,10 +23,10 @@
 
 #include "common.h"
 
-#include <mutex>
-#include <unordered_map>
-#include <map>
-#include <mutex>
+at::Tensor dense_8p_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
+                        int64_t act);                      // gemm8p.hip
+at::Tensor hash_dropout(at::Tensor x, at::Tensor seed, double p,
+                        int64_t salt);                     // kernels.hip
 
 #define BK 64
 #define LDS_STRIDE (BK + 8)   // row stride 144 B (16 B aligned)
@@ -168,10 +170,12 @@ void tiled_gemm_kernel(const bf16* __restrict__ A,    // [M,K]
 }
 
 // ---------------------------------------------------------------------
-// skinny kernel: M <= 32; grid (ceil(N/64), SPLITK); 4 waves of 16 cols;
-// A fragments straight from global (x is L2-resident and tiny), W
-// fragments streamed from global.  SPLITK == 1 stores the final bf16;
-// otherwise fp32 atomics into a workspace + separate epilogue.
+// skinny kernel: M <= RF*16; grid (ceil(N/64), splitk); 4 waves of 16
+// cols; A fragments straight from global (x is L2-resident and tiny), W
+// fragments streamed from global.  Yf == null stores the final bf16
+// (needs splitk == 1); otherwise block row kq stores its K-chunk's
+// partial sums into fp32 slab kq and a separate epilogue kernel combines
+// (an empty trailing chunk stores zeros).
 // ---------------------------------------------------------------------
 
 template <int RF>
@@ -180,10 +184,8 @@ void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
                         const bf16* __restrict__ W,   // [N,K]
                         const bf16* __restrict__ bias,
                         bf16* __restrict__ Y,         // [M,N]
-                        float* __restrict__ Yf,       // slabs (splitk>1)
-                        uint32_t* __restrict__ cnt,   // per-tile monotonic
+                        float* __restrict__ Yf,       // [splitk,M,N] slabs
                         int M, int N, int K, int act, int splitk) {
-    __shared__ uint32_t last_flag;    // the ONLY shared object
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int n0 = blockIdx.x * 64 + wave * 16;
@@ -236,8 +238,8 @@ void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
     }
 
     const int col = n0 + (lane & 15);
-    if (splitk == 1) {
-        if (!active || col >= N) return;
+    if (!active || col >= N) return;
+    if (Yf == nullptr) {
         float bv = (bias != nullptr) ? bf2f(bias[col]) : 0.f;
 #pragma unroll
         for (int mi = 0; mi < RF; ++mi)
@@ -251,50 +253,19 @@ void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
         return;
     }
 
-    // ---- split-K slab store + in-launch combine (agent-scope
-    // release/acquire hand-off, monotonic per-tile ticket counter) ----
-    if (active && col < N) {
-        float* slab = Yf + (int64_t)kq * M * N;
+    // split-K slab store; the caller's epilogue kernel reduces
+    float* slab = Yf + (int64_t)kq * M * N;
 #pragma unroll
-        for (int mi = 0; mi < RF; ++mi)
+    for (int mi = 0; mi < RF; ++mi)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = mi * 16 + (lane >> 4) * 4 + r;
-                if (row < M)
-                    slab[(int64_t)row * N + col] = acc[mi][r];
-            }
-    }
-    if (cnt == nullptr) return;   // slab mode: a separate epilogue reduces
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        uint32_t old = __hip_atomic_fetch_add(
-            &cnt[blockIdx.x], 1u, __ATOMIC_RELAXED,
-            __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = (((old + 1) % (uint32_t)splitk) == 0u) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (last_flag == 0u) return;
-    if (threadIdx.x == 0)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    __syncthreads();
-
-    // reducer: this block sums all slabs for its 64-column tile
-    int ncols = min(64, N - blockIdx.x * 64);
-    int nel = M * ncols;
-    for (int i = threadIdx.x; i < nel; i += (int)blockDim.x) {
-        int row = i / ncols;
-        int c = blockIdx.x * 64 + (i % ncols);
-        float vsum = 0.f;
-        for (int q = 0; q < splitk; ++q)
-            vsum += Yf[(int64_t)q * M * N + (int64_t)row * N + c];
-        if (bias != nullptr) vsum += bf2f(bias[c]);
-        Y[(int64_t)row * N + c] = f2bf(apply_act(vsum, act));
-    }
+        for (int r = 0; r < 4; ++r) {
+            int row = mi * 16 + (lane >> 4) * 4 + r;
+            if (row < M)
+                slab[(int64_t)row * N + col] = acc[mi][r];
+        }
 }
 
+// split-K combine + bias/act for both GEMM kernels' fp32 slabs
 __global__ void skinny_epilogue_kernel(const float* __restrict__ Yf,
                                        const bf16* __restrict__ bias,
                                        bf16* __restrict__ Y,
@@ -302,8 +273,7 @@ __global__ void skinny_epilogue_kernel(const float* __restrict__ Yf,
                                        int splitk) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    float v = 0.f;
-    for (int k = 0; k < splitk; ++k) v += Yf[k * n + idx];
+    float v = sum_slabs(Yf, n, idx, splitk);
     if (bias != nullptr) v += bf2f(bias[idx % N]);
     Y[idx] = f2bf(apply_act(v, act));
 }
@@ -314,37 +284,85 @@ __global__ void dense_glds_kernel(const bf16* __restrict__ A,
                                   bf16* __restrict__ Y,
                                   int M, int N, int K, int act);
 
-// persistent per-grid ticket counters for the in-launch split-K
-// combine (monotonic, modulo-read — never reset, so graph replays and
-// repeated launches stay correct; zero-initialized once per size)
-static at::Tensor _skinny_cnt(int nblocks, const at::TensorOptions& o) {
-    static std::unordered_map<int, at::Tensor> cache;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cache.find(nblocks);
-    if (it == cache.end())
-        it = cache.emplace(nblocks,
-                           at::zeros({nblocks},
-                                     o.dtype(at::kInt))).first;
-    return it->second;
+// ---------------------------------------------------------------------
+// host side: one launch function per kernel family
+// ---------------------------------------------------------------------
+
+static bool is_skinny(int64_t M, int64_t K) {
+    return M <= 128 && K % 32 == 0;
 }
 
-static bool _skinny_fused() {
-    // DEFAULT OFF: the in-launch combine measured 6.87 vs 6.19 ms/step
-    // on the flagship (r02 same-box A/B) — at these B=32 shapes the
-    // last-arriving block's serial slab read blocks the dependent next
-    // kernel, while the separate 256-block epilogue parallelizes it.
-    // Kept behind SAT_SKINNY_FUSED=1 for larger-M experiments.
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("SAT_SKINNY_FUSED");
-        v = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
-    return v == 1;
+// skinny grid: 64-column blocks, K split across blocks until ~3/4 of the
+// 256 CUs have one (every split keeps at least two 32-wide MFMA steps)
+struct SkinnyPlan { int nblocks, splitk; };
+
+static SkinnyPlan skinny_plan(int64_t N, int64_t K) {
+    int nblocks = cdiv(N, 64);
+    int splitk = 1;
+    while (nblocks * splitk < 192 && splitk < 8 &&
+           (int)(K / 32) >= 2 * splitk)
+        splitk *= 2;
+    return {nblocks, splitk};
 }
 
-at::Tensor dense_fwd_out(at::Tensor x, at::Tensor w, at::Tensor bias,
-                         int64_t act, at::Tensor out) {
+// the one skinny launch (RF by M).  yf == null: bias/act and the final
+// bf16 into y, plan.splitk must be 1; otherwise fp32 partial sums into
+// the yf slabs and bias / y / act are unused.
+static void launch_skinny(hipStream_t stream, const at::Tensor& x,
+                          const at::Tensor& w, const bf16* bias, bf16* y,
+                          float* yf, int act, SkinnyPlan plan) {
+    const int M = x.size(0), K = x.size(1), N = w.size(0);
+    TORCH_CHECK(is_skinny(M, K),
+                "skinny GEMM: M <= 128 and K % 32 == 0 only");
+    auto kernel = M <= 32 ? skinny_gemm_kernel<2>
+                : M <= 64 ? skinny_gemm_kernel<4>
+                          : skinny_gemm_kernel<8>;
+    hipLaunchKernelGGL(kernel, dim3(plan.nblocks, plan.splitk), dim3(256),
+                       0, stream, (const bf16*)x.data_ptr(),
+                       (const bf16*)w.data_ptr(), bias, y, yf, M, N, K,
+                       act, plan.splitk);
+}
+
+// slab-mode skinny GEMM for entry points that bring their own epilogue:
+// returns the [splitk, M, N] fp32 partial sums of x @ w^T
+static at::Tensor skinny_slabs(hipStream_t stream, const at::Tensor& x,
+                               const at::Tensor& w) {
+    SkinnyPlan plan = skinny_plan(w.size(0), x.size(1));
+    auto yf = at::empty({plan.splitk, x.size(0), w.size(0)},
+                        x.options().dtype(at::kFloat));
+    launch_skinny(stream, x, w, nullptr, nullptr, (float*)yf.data_ptr(),
+                  ACT_NONE, plan);
+    return yf;
+}
+
+// the one tiled launch: 128x64 tile for N <= 512, else 128x128.
+// yf != null: split-K slab mode (grid z = splitk, kchunk of K each)
+static void launch_tiled(hipStream_t stream, const at::Tensor& x,
+                         const at::Tensor& w, const bf16* bias, bf16* y,
+                         float* yf, int act, int splitk, int kchunk) {
+    const int M = x.size(0), K = x.size(1), N = w.size(0);
+    const bool narrow = N <= 512;
+    auto kernel = narrow ? tiled_gemm_kernel<4, 1, 2, 4>
+                         : tiled_gemm_kernel<2, 2, 4, 4>;
+    dim3 grid(cdiv(N, narrow ? 64 : 128), cdiv(M, 128), splitk);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream,
+                       (const bf16*)x.data_ptr(),
+                       (const bf16*)w.data_ptr(), bias, y, M, N, K, act,
+                       yf, kchunk);
+}
+
+// y[M,N] = act(sum of the yf slabs + bias)
+static void launch_epilogue(hipStream_t stream, const at::Tensor& yf,
+                            const bf16* bias, at::Tensor& y, int act) {
+    int64_t n = y.numel();
+    hipLaunchKernelGGL(skinny_epilogue_kernel, dim3(cdiv(n, 256)),
+                       dim3(256), 0, stream, (const float*)yf.data_ptr(),
+                       bias, (bf16*)y.data_ptr(), n, (int)y.size(1), act,
+                       (int)yf.size(0));
+}
+
+at::Tensor dense_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
+                     int64_t act) {
     CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
     CHECK_GPU(w); CHECK_CONTIG(w); CHECK_BF16(w);
     TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "dense_fwd expects 2-D inputs");
@@ -357,82 +375,30 @@ at::Tensor dense_fwd_out(at::Tensor x, at::Tensor w, at::Tensor bias,
         TORCH_CHECK(bias.numel() == N, "bias size mismatch");
         bias_ptr = (const bf16*)bias.data_ptr();
     }
-    at::Tensor y;
-    if (out.defined() && out.numel() > 0) {
-        CHECK_CONTIG(out); CHECK_BF16(out);
-        TORCH_CHECK(out.numel() == M * N, "out size mismatch");
-        y = out;
-    } else {
-        y = at::empty({M, N}, x.options());
-    }
-    hipStream_t stream = at::cuda::getCurrentCUDAStream();
-
-    if (M <= 128 && K % 32 == 0) {
-        // skinny path with split-K chosen to fill the 256-CU chip
-        int nblocks = cdiv(N, 64);
-        int splitk = 1;
-        while (nblocks * splitk < 192 && splitk < 8 &&
-               (int)(K / 32) >= 2 * splitk)
-            splitk *= 2;
-#define LAUNCH_SKINNY(RF, GRID, BIAS, YPTR, YFPTR, SPLITK) \
-        hipLaunchKernelGGL((skinny_gemm_kernel<RF>), GRID, dim3(256), 0, \
-                           stream, (const bf16*)x.data_ptr(), \
-                           (const bf16*)w.data_ptr(), BIAS, YPTR, YFPTR, \
-                           nullptr, (int)M, (int)N, (int)K, (int)act, \
-                           SPLITK)
-        if (splitk == 1) {
-            if (M <= 32)
-                LAUNCH_SKINNY(2, dim3(nblocks, 1), bias_ptr,
-                              (bf16*)y.data_ptr(), nullptr, 1);
-            else if (M <= 64)
-                LAUNCH_SKINNY(4, dim3(nblocks, 1), bias_ptr,
-                              (bf16*)y.data_ptr(), nullptr, 1);
-            else
-                LAUNCH_SKINNY(8, dim3(nblocks, 1), bias_ptr,
-                              (bf16*)y.data_ptr(), nullptr, 1);
-        } else if (_skinny_fused()) {
-            // in-launch combine: each 64-col tile's last-arriving block
-            // reduces the slabs (agent-scope release/acquire + ticket,
-            // §6 G16 recipe) — no epilogue launch
-            auto yf = at::empty({splitk, M, N},
-                                x.options().dtype(at::kFloat));
-            auto cnt = _skinny_cnt(nblocks, x.options());
-#define LAUNCH_SKF(RF)             hipLaunchKernelGGL((skinny_gemm_kernel<RF>),                                dim3(nblocks, splitk), dim3(256), 0,                                stream, (const bf16*)x.data_ptr(),                                (const bf16*)w.data_ptr(), bias_ptr,                                (bf16*)y.data_ptr(),                                (float*)yf.data_ptr(),                                (uint32_t*)cnt.data_ptr(), (int)M,                                (int)N, (int)K, (int)act, splitk)
-            if (M <= 32) LAUNCH_SKF(2);
-            else if (M <= 64) LAUNCH_SKF(4);
-            else LAUNCH_SKF(8);
-#undef LAUNCH_SKF
-        } else {
-            auto yf = at::empty({splitk, M, N},
-                                x.options().dtype(at::kFloat));
-            if (M <= 32)
-                LAUNCH_SKINNY(2, dim3(nblocks, splitk), nullptr, nullptr,
-                              (float*)yf.data_ptr(), splitk);
-            else if (M <= 64)
-                LAUNCH_SKINNY(4, dim3(nblocks, splitk), nullptr, nullptr,
-                              (float*)yf.data_ptr(), splitk);
-            else
-                LAUNCH_SKINNY(8, dim3(nblocks, splitk), nullptr, nullptr,
-                              (float*)yf.data_ptr(), splitk);
-            int64_t n = M * N;
-            hipLaunchKernelGGL(skinny_epilogue_kernel,
-                               dim3(cdiv(n, 256)), dim3(256), 0, stream,
-                               (const float*)yf.data_ptr(), bias_ptr,
-                               (bf16*)y.data_ptr(), n, (int)N, (int)act,
-                               splitk);
-        }
-#undef LAUNCH_SKINNY
-    } else if (M >= 16384 && N >= 256 && N % 8 == 0 && K % 64 == 0
-               && K >= 128 && !(out.defined() && out.numel() > 0)) {
+    const bool skinny = is_skinny(M, K);
+    if (!skinny && M >= 16384 && N >= 256 && N % 8 == 0 && K % 64 == 0
+        && K >= 128) {
         // big-M dense shapes: the 8-phase deep-pipelined 256^2 tile
         // (gemm8p.hip; the 2-barrier glds tile measured only ~190 TF
         // here — short K leaves it prologue-bound)
-        extern at::Tensor dense_8p_fwd(at::Tensor, at::Tensor,
-                                       at::Tensor, int64_t);
-        at::Tensor bb = (bias_ptr != nullptr) ? bias : at::Tensor();
-        return dense_8p_fwd(x, w, bb, act);
+        return dense_8p_fwd(x, w, bias_ptr != nullptr ? bias : at::Tensor(),
+                            act);
+    }
+    auto y = at::empty({M, N}, x.options());
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+
+    if (skinny) {
+        SkinnyPlan plan = skinny_plan(N, K);
+        if (plan.splitk == 1) {
+            launch_skinny(stream, x, w, bias_ptr, (bf16*)y.data_ptr(),
+                          nullptr, (int)act, plan);
+        } else {
+            auto yf = skinny_slabs(stream, x, w);
+            launch_epilogue(stream, yf, bias_ptr, y, (int)act);
+        }
     } else if (M >= 16384 && N % 128 == 0 && K % 64 == 0) {
-        // (retained) glds-staged 128^2 tile
+        // (retained) glds-staged 128^2 tile: the big-M shapes the
+        // 8-phase kernel does not take (N < 256 or K < 128)
         dim3 grid(cdiv(N, 128), cdiv(M, 128));
         hipLaunchKernelGGL(dense_glds_kernel, grid, dim3(256), 0,
                            stream,
@@ -445,74 +411,29 @@ at::Tensor dense_fwd_out(at::Tensor x, at::Tensor w, at::Tensor bias,
         // leave the 2-barrier tile grid at 40-60 blocks on 256 CUs;
         // split K until ~2/3 of the chip has a block (measured 28-42 TF
         // -> the slab+epilogue pair more than doubles it)
-        int bn_t = (N <= 512) ? 64 : 128;
-        int tiles = cdiv(N, bn_t) * cdiv(M, 128);
+        int tiles = cdiv(N, N <= 512 ? 64 : 128) * cdiv(M, 128);
         int splitk = 1;
         while (tiles * splitk < 160 && splitk < 8
                && K >= 128 * 2 * splitk)
             splitk *= 2;
         int kchunk = cdiv(cdiv(K, splitk), 64) * 64;
         splitk = cdiv(K, kchunk);
-        float* yf_ptr = nullptr;
-        at::Tensor yf;
-        if (splitk > 1) {
-            yf = at::empty({splitk, M, N},
-                           x.options().dtype(at::kFloat));
-            yf_ptr = (float*)yf.data_ptr();
-        }
-        dim3 grid(cdiv(N, bn_t), cdiv(M, 128), splitk);
-        if (N <= 512)
-            hipLaunchKernelGGL((tiled_gemm_kernel<4, 1, 2, 4>), grid,
-                               dim3(256), 0, stream,
-                               (const bf16*)x.data_ptr(),
-                               (const bf16*)w.data_ptr(), bias_ptr,
-                               (bf16*)y.data_ptr(), (int)M, (int)N,
-                               (int)K, (int)act, yf_ptr, kchunk);
-        else
-            hipLaunchKernelGGL((tiled_gemm_kernel<2, 2, 4, 4>), grid,
-                               dim3(256), 0, stream,
-                               (const bf16*)x.data_ptr(),
-                               (const bf16*)w.data_ptr(), bias_ptr,
-                               (bf16*)y.data_ptr(), (int)M, (int)N,
-                               (int)K, (int)act, yf_ptr, kchunk);
-        if (splitk > 1) {
-            int64_t n = M * N;
-            hipLaunchKernelGGL(skinny_epilogue_kernel,
-                               dim3(cdiv(n, 256)), dim3(256), 0, stream,
-                               (const float*)yf.data_ptr(), bias_ptr,
-                               (bf16*)y.data_ptr(), n, (int)N, (int)act,
-                               splitk);
+        if (splitk == 1) {
+            launch_tiled(stream, x, w, bias_ptr, (bf16*)y.data_ptr(),
+                         nullptr, (int)act, 1, kchunk);
+        } else {
+            auto yf = at::empty({splitk, M, N},
+                                x.options().dtype(at::kFloat));
+            launch_tiled(stream, x, w, bias_ptr, (bf16*)y.data_ptr(),
+                         (float*)yf.data_ptr(), (int)act, splitk, kchunk);
+            launch_epilogue(stream, yf, bias_ptr, y, (int)act);
         }
     }
     HIP_OK(hipGetLastError());
     return y;
 }
 
-at::Tensor dense_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
-                     int64_t act) {
-    return dense_fwd_out(x, w, bias, act, at::Tensor());
-}
-
 // ---- GEMM + counter-hash dropout fused into the split-K epilogue ----
-// (same hash as hash_dropout_kernel — backward/forward mask pairs must
-// regenerate identically)
-
-__device__ __forceinline__ uint32_t mix3g(uint32_t a, uint32_t b,
-                                          uint32_t c) {
-    uint32_t h = a * 0x9E3779B1u ^ b * 0x85EBCA77u ^ c * 0xC2B2AE3Du;
-    h ^= h >> 16; h *= 0x7FEB352Du;
-    h ^= h >> 15; h *= 0x846CA68Bu;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ float dscaleg(uint32_t seed, int salt,
-                                         uint32_t idx, float p) {
-    if (p <= 0.f) return 1.f;
-    uint32_t h = mix3g(seed, (uint32_t)salt, idx);
-    float u = (h >> 8) * (1.0f / 16777216.0f);
-    return u >= p ? 1.0f / (1.0f - p) : 0.0f;
-}
 
 __global__ void skinny_epilogue_drop_kernel(
         const float* __restrict__ Yf, bf16* __restrict__ Y,
@@ -520,9 +441,8 @@ __global__ void skinny_epilogue_drop_kernel(
         float p, int salt) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    float v = 0.f;
-    for (int k = 0; k < splitk; ++k) v += Yf[k * n + idx];
-    v *= dscaleg((uint32_t)(*seed_p), salt, (uint32_t)idx, p);
+    float v = sum_slabs(Yf, n, idx, splitk);
+    v *= drop_scale((uint32_t)(*seed_p), salt, (uint32_t)idx, p);
     Y[idx] = f2bf(v);
 }
 
@@ -534,42 +454,47 @@ at::Tensor dense_fwd_drop(at::Tensor x, at::Tensor w, at::Tensor seed,
     CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
     CHECK_GPU(w); CHECK_CONTIG(w); CHECK_BF16(w);
     int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-    hipStream_t stream = at::cuda::getCurrentCUDAStream();
-    if (p <= 0.0 || M > 128 || K % 32 != 0) {
+    if (p <= 0.0 || !is_skinny(M, K)) {
         // non-skinny shapes: plain GEMM + the separate dropout pass
-        // (defined in kernels.hip; same hash)
-        extern at::Tensor hash_dropout(at::Tensor, at::Tensor, double,
-                                       int64_t);
-        auto y = dense_fwd_out(x, w, at::Tensor(), 0, at::Tensor());
+        auto y = dense_fwd(x, w, at::Tensor(), ACT_NONE);
         return p > 0.0 ? hash_dropout(y, seed, p, salt) : y;
     }
     auto y = at::empty({M, N}, x.options());
-    int nblocks = cdiv(N, 64);
-    int splitk = 1;
-    while (nblocks * splitk < 192 && splitk < 8 &&
-           (int)(K / 32) >= 2 * splitk)
-        splitk *= 2;
-    auto yf = at::empty({splitk, M, N}, x.options().dtype(at::kFloat));
-#define LAUNCH_SK(RF)     hipLaunchKernelGGL((skinny_gemm_kernel<RF>), dim3(nblocks, splitk),                        dim3(256), 0, stream, (const bf16*)x.data_ptr(),                        (const bf16*)w.data_ptr(), nullptr, nullptr,                        (float*)yf.data_ptr(), nullptr, (int)M, (int)N,                        (int)K, 0, splitk)
-    if (M <= 32) LAUNCH_SK(2);
-    else if (M <= 64) LAUNCH_SK(4);
-    else LAUNCH_SK(8);
-#undef LAUNCH_SK
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+    auto yf = skinny_slabs(stream, x, w);
     int64_t n = M * N;
     hipLaunchKernelGGL(skinny_epilogue_drop_kernel,
                        dim3(cdiv(n, 256)), dim3(256), 0, stream,
                        (const float*)yf.data_ptr(), (bf16*)y.data_ptr(),
-                       (const int64_t*)seed.data_ptr(), n, splitk,
-                       (float)p, (int)salt);
+                       (const int64_t*)seed.data_ptr(), n,
+                       (int)yf.size(0), (float)p, (int)salt);
     HIP_OK(hipGetLastError());
     return y;
 }
 
-// ---- fused skinny epilogues for the BPTT step chain (B <= 32) ----
+// ---- fused skinny epilogues for the BPTT step chain (B <= 128) ----
+
+// the four pre-activation gates of (b, hh): split-K sum + bias, written
+// to gates[] as bf16 (saved for backward) and returned in fp32
+__device__ __forceinline__ void sum_gates(const float* __restrict__ Yf,
+                                          const bf16* __restrict__ bias,
+                                          bf16* __restrict__ gates,
+                                          int B, int H, int b, int hh,
+                                          int splitk, float g[4]) {
+    int64_t n = (int64_t)B * 4 * H;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        int64_t off = (int64_t)b * 4 * H + q * H + hh;
+        float acc = sum_slabs(Yf, n, off, splitk);
+        if (bias != nullptr) acc += bf2f(bias[q * H + hh]);
+        gates[off] = f2bf(acc);
+        g[q] = acc;
+    }
+}
 
 // gates epilogue + LSTM pointwise: thread per (b,h) sums the 4 gate
-// elements across split-K slabs, applies TF LSTM gate math, writes the
-// bf16 gates (saved for backward) plus h_raw and c_new.
+// elements across split-K slabs, applies the LSTM gate math, writes the
+// bf16 gates plus h_raw and c_new.
 __global__ void skinny_epi_lstm_kernel(const float* __restrict__ Yf,
                                        const bf16* __restrict__ bias,
                                        const bf16* __restrict__ c_prev,
@@ -580,24 +505,10 @@ __global__ void skinny_epi_lstm_kernel(const float* __restrict__ Yf,
                                        float fb) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * H) return;
-    int b = idx / H, hh = idx % H;
-    int64_t n = (int64_t)B * 4 * H;
-    float g[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int64_t off = (int64_t)b * 4 * H + q * H + hh;
-        float acc = 0.f;
-        for (int k = 0; k < splitk; ++k) acc += Yf[k * n + off];
-        if (bias != nullptr) acc += bf2f(bias[q * H + hh]);
-        gates[off] = f2bf(acc);
-        g[q] = acc;
-    }
-    float gi = sigmoidf(g[0]);
-    float gj = tanhf(g[1]);
-    float gf = sigmoidf(g[2] + fb);
-    float go = sigmoidf(g[3]);
-    float cn = bf2f(c_prev[idx]) * gf + gi * gj;
-    h_out[idx] = f2bf(tanhf(cn) * go);
+    float g[4], cn, h;
+    sum_gates(Yf, bias, gates, B, H, idx / H, idx % H, splitk, g);
+    lstm_cell_fwd(g, bf2f(c_prev[idx]), fb, cn, h);
+    h_out[idx] = f2bf(h);
     c_out[idx] = f2bf(cn);
 }
 
@@ -605,103 +516,26 @@ std::vector<at::Tensor> dense_lstm_fwd(at::Tensor xh, at::Tensor wl,
                                        at::Tensor bl, at::Tensor c_prev,
                                        double fb) {
     // gates = xh @ wl^T + bl ; (h_raw, c_new) = LSTM(gates, c_prev)
-    int64_t M = xh.size(0), K = xh.size(1), N = wl.size(0);
+    int64_t M = xh.size(0), N = wl.size(0);
     int B = c_prev.size(0), H = c_prev.size(1);
-    TORCH_CHECK(M == B && N == 4 * H && M <= 128 && K % 32 == 0);
+    TORCH_CHECK(M == B && N == 4 * H);
     auto gates = at::empty({M, N}, xh.options());
     auto h_out = at::empty_like(c_prev);
     auto c_out = at::empty_like(c_prev);
-    int nblocks = cdiv(N, 64);
-    int splitk = 1;
-    while (nblocks * splitk < 192 && splitk < 8 &&
-           (int)(K / 32) >= 2 * splitk)
-        splitk *= 2;
-    auto yf = at::empty({splitk, M, N}, xh.options().dtype(at::kFloat));
     hipStream_t s = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_SLSTM(RF) \
-    hipLaunchKernelGGL((skinny_gemm_kernel<RF>), dim3(nblocks, splitk), \
-                       dim3(256), 0, s, (const bf16*)xh.data_ptr(), \
-                       (const bf16*)wl.data_ptr(), nullptr, nullptr, \
-                       (float*)yf.data_ptr(), nullptr, (int)M, (int)N, \
-                       (int)K, ACT_NONE, splitk)
-    if (M <= 32) LAUNCH_SLSTM(2);
-    else if (M <= 64) LAUNCH_SLSTM(4);
-    else LAUNCH_SLSTM(8);
-#undef LAUNCH_SLSTM
+    auto yf = skinny_slabs(s, xh, wl);
     hipLaunchKernelGGL(skinny_epi_lstm_kernel,
                        dim3(cdiv(B * H, 256)), dim3(256), 0, s,
                        (const float*)yf.data_ptr(),
                        (const bf16*)bl.data_ptr(),
                        (const bf16*)c_prev.data_ptr(),
                        (bf16*)gates.data_ptr(), (bf16*)h_out.data_ptr(),
-                       (bf16*)c_out.data_ptr(), B, H, splitk, (float)fb);
+                       (bf16*)c_out.data_ptr(), B, H, (int)yf.size(0),
+                       (float)fb);
     HIP_OK(hipGetLastError());
     return {gates, h_out, c_out};
 }
 
-// epilogue + activation + hash dropout: writes both y and dropout(y)
-__global__ void skinny_epi_drop_kernel(const float* __restrict__ Yf,
-                                       const bf16* __restrict__ bias,
-                                       const int64_t* __restrict__ seed_p,
-                                       bf16* __restrict__ y,
-                                       bf16* __restrict__ ydrop,
-                                       int64_t n, int N, int act,
-                                       int splitk, float p, int salt) {
-    const uint32_t seed = (uint32_t)(*seed_p);
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    float v = 0.f;
-    for (int k = 0; k < splitk; ++k) v += Yf[k * n + idx];
-    if (bias != nullptr) v += bf2f(bias[idx % N]);
-    v = apply_act(v, act);
-    y[idx] = f2bf(v);
-    float sc = 1.f;
-    if (p > 0.f) {
-        uint32_t h = (seed * 0x9E3779B1u) ^
-                     ((uint32_t)salt * 0x85EBCA77u) ^
-                     ((uint32_t)idx * 0xC2B2AE3Du);
-        h ^= h >> 16; h *= 0x7FEB352Du;
-        h ^= h >> 15; h *= 0x846CA68Bu;
-        h ^= h >> 16;
-        float u = (h >> 8) * (1.0f / 16777216.0f);
-        sc = u >= p ? 1.0f / (1.0f - p) : 0.0f;
-    }
-    ydrop[idx] = f2bf(v * sc);
-}
-
-void dense_drop_fwd(at::Tensor x, at::Tensor w, at::Tensor b, int64_t act,
-                    at::Tensor seed, double p, int64_t salt,
-                    at::Tensor y, at::Tensor ydrop) {
-    int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-    TORCH_CHECK(M <= 128 && K % 32 == 0);
-    int nblocks = cdiv(N, 64);
-    int splitk = 1;
-    while (nblocks * splitk < 192 && splitk < 8 &&
-           (int)(K / 32) >= 2 * splitk)
-        splitk *= 2;
-    auto yf = at::empty({splitk, M, N}, x.options().dtype(at::kFloat));
-    hipStream_t s = at::cuda::getCurrentCUDAStream();
-#define LAUNCH_SDROP(RF) \
-    hipLaunchKernelGGL((skinny_gemm_kernel<RF>), dim3(nblocks, splitk), \
-                       dim3(256), 0, s, (const bf16*)x.data_ptr(), \
-                       (const bf16*)w.data_ptr(), nullptr, nullptr, \
-                       (float*)yf.data_ptr(), nullptr, (int)M, (int)N, \
-                       (int)K, ACT_NONE, splitk)
-    if (M <= 32) LAUNCH_SDROP(2);
-    else if (M <= 64) LAUNCH_SDROP(4);
-    else LAUNCH_SDROP(8);
-#undef LAUNCH_SDROP
-    int64_t n = M * N;
-    const bf16* bias_ptr = (b.defined() && b.numel() > 0)
-        ? (const bf16*)b.data_ptr() : nullptr;
-    hipLaunchKernelGGL(skinny_epi_drop_kernel, dim3(cdiv(n, 256)),
-                       dim3(256), 0, s,
-                       (const float*)yf.data_ptr(), bias_ptr,
-                       (const int64_t*)seed.data_ptr(),
-                       (bf16*)y.data_ptr(), (bf16*)ydrop.data_ptr(),
-                       n, (int)N, (int)act, splitk, (float)p, (int)salt);
-    HIP_OK(hipGetLastError());
-}
 
 // ---------------------------------------------------------------------
 // glds-staged 128x128 dense GEMM for big-M shapes (the attention
@@ -841,11 +675,10 @@ __global__ void skinny_epi_dx_kernel(const float* __restrict__ Yf,
     const int W = I + H;
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    float g = 0.f;
-    for (int k = 0; k < splitk; ++k) g += Yf[k * n + idx];
+    float g = sum_slabs(Yf, n, idx, splitk);
     int b = (int)(idx / W), j = (int)(idx % W);
     if (j < I) {
-        g *= dscaleg(seed, salt, (uint32_t)(b * I + j), p);
+        g *= drop_scale(seed, salt, (uint32_t)(b * I + j), p);
         if (j < D)
             dpooled[(int64_t)b * D + j] =
                 f2bf(g + bf2f(dpool_dec[(int64_t)b * D + j]));
@@ -866,33 +699,12 @@ std::vector<at::Tensor> dense_dx_fuse(at::Tensor dgates, at::Tensor wl_t,
                                       int64_t D, int64_t E, int64_t H) {
     CHECK_GPU(dgates); CHECK_CONTIG(dgates); CHECK_BF16(dgates);
     CHECK_GPU(wl_t); CHECK_CONTIG(wl_t); CHECK_BF16(wl_t);
-    int64_t M = dgates.size(0), K = dgates.size(1);
-    int64_t N = wl_t.size(0);
+    int64_t M = dgates.size(0), N = wl_t.size(0);
     TORCH_CHECK(N == D + E + H);
-    TORCH_CHECK(M <= 128 && K % 32 == 0,
-                "dense_dx_fuse: skinny shapes only");
     auto dpooled = at::empty({M, D}, dgates.options());
     auto dsth = at::empty({M, H}, dgates.options());
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
-
-    int nblocks = cdiv(N, 64);
-    int splitk = 1;
-    while (nblocks * splitk < 192 && splitk < 8 &&
-           (int)(K / 32) >= 2 * splitk)
-        splitk *= 2;
-    auto yf = at::empty({splitk, M, N}, dgates.options()
-                                            .dtype(at::kFloat));
-#define LAUNCH_SKX(RF) \
-    hipLaunchKernelGGL((skinny_gemm_kernel<RF>), dim3(nblocks, splitk), \
-                       dim3(256), 0, stream, \
-                       (const bf16*)dgates.data_ptr(), \
-                       (const bf16*)wl_t.data_ptr(), nullptr, nullptr, \
-                       (float*)yf.data_ptr(), nullptr, (int)M, (int)N, \
-                       (int)K, 0, splitk)
-    if (M <= 32) LAUNCH_SKX(2);
-    else if (M <= 64) LAUNCH_SKX(4);
-    else LAUNCH_SKX(8);
-#undef LAUNCH_SKX
+    auto yf = skinny_slabs(stream, dgates, wl_t);
     int64_t n = M * N;
     hipLaunchKernelGGL(skinny_epi_dx_kernel, dim3(cdiv(n, 256)),
                        dim3(256), 0, stream,
@@ -903,7 +715,7 @@ std::vector<at::Tensor> dense_dx_fuse(at::Tensor dgates, at::Tensor wl_t,
                        (bf16*)dpooled.data_ptr(),
                        (bf16*)demb_out.data_ptr(),
                        (bf16*)dsth.data_ptr(),
-                       n, splitk, (int)M, (int)D, (int)E, (int)H,
+                       n, (int)yf.size(0), (int)M, (int)D, (int)E, (int)H,
                        (float)p, (int)salt);
     HIP_OK(hipGetLastError());
     return {dpooled, dsth};
@@ -937,39 +749,25 @@ __global__ void skinny_epi_lstm_expand_kernel(
     int b = idx / W, j = idx % W;
     float val;
     if (j < H) {
-        int64_t n = (int64_t)B * 4 * H;
-        float g[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int64_t off = (int64_t)b * 4 * H + q * H + j;
-            float acc = 0.f;
-            for (int k = 0; k < splitk; ++k) acc += Yf[k * n + off];
-            if (bias != nullptr) acc += bf2f(bias[q * H + j]);
-            gates[off] = f2bf(acc);
-            g[q] = acc;
-        }
-        float gi = sigmoidf(g[0]);
-        float gj = tanhf(g[1]);
-        float gf = sigmoidf(g[2] + fb);
-        float go = sigmoidf(g[3]);
-        float cn = bf2f(c_prev[(int64_t)b * H + j]) * gf + gi * gj;
-        float h = tanhf(cn) * go;
+        float g[4], cn, h;
+        sum_gates(Yf, bias, gates, B, H, b, j, splitk, g);
+        lstm_cell_fwd(g, bf2f(c_prev[(int64_t)b * H + j]), fb, cn, h);
         c_out[(int64_t)b * H + j] = f2bf(cn);
         uint32_t hidx = (uint32_t)(b * H + j);
-        float ot = h * dscaleg(seed, s + 4, hidx, p_lstm);
+        float ot = h * drop_scale(seed, s + 4, hidx, p_lstm);
         sth_t[(int64_t)b * H + j] =
-            f2bf(h * dscaleg(seed, s + 5, hidx, p_lstm));
+            f2bf(h * drop_scale(seed, s + 5, hidx, p_lstm));
         if (od_next != nullptr)
             od_next[(int64_t)b * H + j] =
-                f2bf(ot * dscaleg(seed, s + 16 + 1, hidx, p_fc));
+                f2bf(ot * drop_scale(seed, s + 16 + 1, hidx, p_fc));
         val = ot;
     } else if (j < H + D) {
         val = bf2f(pooled[(int64_t)b * D + (j - H)]);
     } else {
         val = bf2f(table[ids[b] * E + (j - H - D)]);
     }
-    expdrop[idx] = f2bf(val * dscaleg(seed, s + 6,
-                                      (uint32_t)(b * W + j), p_fc));
+    expdrop[idx] = f2bf(val * drop_scale(seed, s + 6,
+                                         (uint32_t)(b * W + j), p_fc));
 }
 
 std::vector<at::Tensor> dense_lstm_expand_fwd(
@@ -977,33 +775,15 @@ std::vector<at::Tensor> dense_lstm_expand_fwd(
         at::Tensor pooled, at::Tensor table, at::Tensor ids,
         at::Tensor seed, at::Tensor expdrop, at::Tensor od_next,
         double fb, double p_lstm, double p_fc, int64_t s) {
-    int64_t M = xh.size(0), K = xh.size(1), N = wl.size(0);
+    int64_t M = xh.size(0), N = wl.size(0);
     int B = c_prev.size(0), H = c_prev.size(1);
     int D = pooled.size(1), E = table.size(1);
-    TORCH_CHECK(M == B && N == 4 * H && M <= 128 && K % 32 == 0);
+    TORCH_CHECK(M == B && N == 4 * H);
     auto gates = at::empty({M, N}, xh.options());
     auto c_out = at::empty({B, H}, xh.options());
     auto sth_t = at::empty({B, H}, xh.options());
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
-
-    int nblocks = cdiv(N, 64);
-    int splitk = 1;
-    while (nblocks * splitk < 192 && splitk < 8 &&
-           (int)(K / 32) >= 2 * splitk)
-        splitk *= 2;
-    auto yf = at::empty({splitk, M, N},
-                        xh.options().dtype(at::kFloat));
-#define LAUNCH_SKL(RF) \
-    hipLaunchKernelGGL((skinny_gemm_kernel<RF>), dim3(nblocks, splitk), \
-                       dim3(256), 0, stream, \
-                       (const bf16*)xh.data_ptr(), \
-                       (const bf16*)wl.data_ptr(), nullptr, nullptr, \
-                       (float*)yf.data_ptr(), nullptr, (int)M, (int)N, \
-                       (int)K, 0, splitk)
-    if (M <= 32) LAUNCH_SKL(2);
-    else if (M <= 64) LAUNCH_SKL(4);
-    else LAUNCH_SKL(8);
-#undef LAUNCH_SKL
+    auto yf = skinny_slabs(stream, xh, wl);
     const bf16* bias_ptr = nullptr;
     if (bl.defined() && bl.numel() > 0)
         bias_ptr = (const bf16*)bl.data_ptr();
@@ -1023,7 +803,7 @@ std::vector<at::Tensor> dense_lstm_expand_fwd(
                        (bf16*)c_out.data_ptr(),
                        (bf16*)sth_t.data_ptr(),
                        (bf16*)expdrop.data_ptr(), od_ptr,
-                       B, H, D, E, splitk,
+                       B, H, D, E, (int)yf.size(0),
                        (float)fb, (float)p_lstm, (float)p_fc, (int)s);
     HIP_OK(hipGetLastError());
     return {gates, c_out, sth_t};

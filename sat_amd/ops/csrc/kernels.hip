@@ -20,13 +20,13 @@ __global__ void lstm_pw_fwd_kernel(const bf16* __restrict__ gates,
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * H) return;
     int b = idx / H, hh = idx % H;
-    const bf16* g = gates + (int64_t)b * 4 * H;
-    float gi = sigmoidf(bf2f(g[hh]));
-    float gj = tanhf(bf2f(g[H + hh]));
-    float gf = sigmoidf(bf2f(g[2 * H + hh]) + fb);
-    float go = sigmoidf(bf2f(g[3 * H + hh]));
-    float cn = bf2f(c[idx]) * gf + gi * gj;
-    h_out[idx] = f2bf(tanhf(cn) * go);
+    const bf16* gp = gates + (int64_t)b * 4 * H + hh;
+    float g[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q] = bf2f(gp[q * H]);
+    float cn, h;
+    lstm_cell_fwd(g, bf2f(c[idx]), fb, cn, h);
+    h_out[idx] = f2bf(h);
     c_out[idx] = f2bf(cn);
 }
 
@@ -40,23 +40,16 @@ __global__ void lstm_pw_bwd_kernel(const bf16* __restrict__ gates,
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * H) return;
     int b = idx / H, hh = idx % H;
-    const bf16* g = gates + (int64_t)b * 4 * H;
-    float gi = sigmoidf(bf2f(g[hh]));
-    float gj = tanhf(bf2f(g[H + hh]));
-    float gf = sigmoidf(bf2f(g[2 * H + hh]) + fb);
-    float go = sigmoidf(bf2f(g[3 * H + hh]));
-    float cp = bf2f(c[idx]);
-    float cn = cp * gf + gi * gj;
-    float tc = tanhf(cn);
-    float dhv = bf2f(dh[idx]);
+    const bf16* gp = gates + (int64_t)b * 4 * H + hh;
+    float g[4], dg[4], dcp;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q] = bf2f(gp[q * H]);
     float dcv = (dc != nullptr) ? bf2f(dc[idx]) : 0.f;
-    float dct = dcv + dhv * go * (1.f - tc * tc);
-    bf16* dg = dgates + (int64_t)b * 4 * H;
-    dg[hh]         = f2bf(dct * gj * gi * (1.f - gi));       // di
-    dg[H + hh]     = f2bf(dct * gi * (1.f - gj * gj));       // dj
-    dg[2 * H + hh] = f2bf(dct * cp * gf * (1.f - gf));       // df
-    dg[3 * H + hh] = f2bf(dhv * tc * go * (1.f - go));       // do
-    dc_prev[idx]   = f2bf(dct * gf);
+    lstm_cell_bwd(g, bf2f(c[idx]), bf2f(dh[idx]), dcv, fb, dg, dcp);
+    bf16* dgp = dgates + (int64_t)b * 4 * H + hh;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dgp[q * H] = f2bf(dg[q]);
+    dc_prev[idx] = f2bf(dcp);
 }
 
 std::vector<at::Tensor> lstm_pointwise_fwd(at::Tensor gates, at::Tensor c,
@@ -146,50 +139,8 @@ at::Tensor act_bwd(at::Tensor dy, at::Tensor y, int64_t act) {
 
 #define MAX_L 1024
 
-// counter-based dropout hash: deterministic in (seed, salt, index), so the
-// backward regenerates the mask with zero storage, and the seed lives in a
-// DEVICE scalar the model advances once per step (hipGraph-safe: replays
-// see fresh masks, unlike a host-baked philox offset).
-__device__ __forceinline__ uint32_t mix3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t h = a * 0x9E3779B1u ^ b * 0x85EBCA77u ^ c * 0xC2B2AE3Du;
-    h ^= h >> 16; h *= 0x7FEB352Du;
-    h ^= h >> 15; h *= 0x846CA68Bu;
-    h ^= h >> 16;
-    return h;
-}
-
-// 8 masks from two hashes (one per 4 bytes): ~4x less ALU than 8
-// per-element hashes.  Used by the attention scores fwd/bwd PAIR only —
-// both sides must derive masks identically.
-__device__ __forceinline__ void drop_scale8(uint32_t seed, int salt,
-                                            uint32_t idx8, float p,
-                                            float* sc) {
-    if (p <= 0.f) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sc[e] = 1.f;
-        return;
-    }
-    uint32_t pq = (uint32_t)(p * 256.0f);
-    float inv = 1.0f / (1.0f - p);
-    uint32_t h1 = mix3(seed, (uint32_t)salt, idx8);
-    uint32_t h2 = mix3(h1, (uint32_t)salt ^ 0xA5A5A5A5u, idx8);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        sc[e] = ((h1 >> (e * 8)) & 0xFFu) >= pq ? inv : 0.f;
-        sc[4 + e] = ((h2 >> (e * 8)) & 0xFFu) >= pq ? inv : 0.f;
-    }
-}
-
-__device__ __forceinline__ float drop_scale(uint32_t seed, int salt,
-                                            uint32_t idx, float p) {
-    if (p <= 0.f) return 1.f;
-    uint32_t h = mix3(seed, (uint32_t)salt, idx);
-    float u = (h >> 8) * (1.0f / 16777216.0f);
-    return u >= p ? 1.0f / (1.0f - p) : 0.0f;
-}
-
 // ---- generic counter-based dropout (used by the hand-written BPTT) ----
-// Same hash as the attention tail: y = x * mask(seed,salt,idx)/(1-p).
+// The counter hash of common.h: y = x * mask(seed,salt,idx)/(1-p).
 // Forward and backward are the same kernel (masks regenerate exactly).
 
 __global__ void hash_dropout_kernel(const bf16* __restrict__ x,

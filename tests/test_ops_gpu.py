@@ -31,6 +31,11 @@ def _rel_err(a, b):
     (32, 5000, 1024),    # decode logits (N edge: 5000 % 128 != 0)
     (100, 130, 72),      # everything-edge
     (1, 16, 8),          # degenerate
+    (48, 320, 96),       # skinny RF=4 (16 masked rows), splitk 2
+    (48, 296, 96),       # same, last block: partial wave + idle wave
+    (128, 200, 160),     # skinny RF=8, partial last 16-column slab,
+                         # splitk 4 with an empty fourth K-chunk
+    (32, 64, 32),        # skinny splitk == 1 direct-store branch
 ])
 @pytest.mark.parametrize('act', [None, 'tanh', 'relu'])
 def test_dense_fwd(M, N, K, act):
@@ -530,56 +535,102 @@ def test_conv1x1_as_gemm_route():
         assert _rel_err(y, ref) < 2e-2, (Cin, Cout)
 
 
-def test_fused_kernels_match_their_unfused_pairs_bitwise():
-    """Every r02 fusion vs the kernel pair it replaced.  Outputs whose
-    math is identical must match BITWISE (dropout masks especially —
-    backward regenerates them from the same counter hash).  Outputs
-    where the fusion keeps fp32 through a stage the pair rounds to bf16
-    (e.g. dxh, h_raw, dt1 intermediates) may differ by ONE bf16
-    rounding — the fused value is the more accurate one."""
+# ---- every r02 fusion vs the kernel pair it replaced ----
+# Outputs whose math is identical must match BITWISE (dropout masks
+# especially — backward regenerates them from the same counter hash).
+# Outputs where the fusion keeps fp32 through a stage the pair rounds to
+# bf16 (e.g. dxh, h_raw, dt1 intermediates) may differ by ONE bf16
+# rounding — the fused value is the more accurate one.
 
-    def _one_ulp(a, b):
-        # bounded by one bf16 rounding of the pair's intermediate,
-        # scaled to the tensor's magnitude (a relative bound would be
-        # wrong under cancellation: x*scale + y with y ~ -x*scale keeps
-        # the intermediate's absolute rounding while the result is ~0)
-        fa, fb = a.float(), b.float()
-        tol = float(fb.abs().max()) * (2.0 ** -7) + 1e-6
-        assert float((fa - fb).abs().max()) <= tol
+def _one_ulp(a, b):
+    # bounded by one bf16 rounding of the pair's intermediate, scaled to
+    # the tensor's magnitude (a relative bound would be wrong under
+    # cancellation: x*scale + y with y ~ -x*scale keeps the
+    # intermediate's absolute rounding while the result is ~0)
+    fa, fb = a.float(), b.float()
+    tol = float(fb.abs().max()) * (2.0 ** -7) + 1e-6
+    assert float((fa - fb).abs().max()) <= tol
+
+
+def _fuse_seed():
+    return torch.tensor(777, dtype=torch.int64, device=DEV)
+
+
+def _empty_bf(*shape):
+    return torch.empty(*shape, dtype=torch.bfloat16, device=DEV)
+
+
+_P_FC, _P_LSTM, _SALT = 0.5, 0.3, 48
+
+# (B,H,D,E): the flagship step; then H=D=E=64, where the gates GEMM has
+# K=192, N=256 -> splitk 4 with a 64-wide chunk, so the fourth K-chunk is
+# empty and its slab must come out as zeros — at B=33 (RF=4, 31 masked
+# rows) and B=128 (RF=8 full)
+_fuse_shapes = pytest.mark.parametrize('B,H,D,E', [
+    (32, 512, 512, 512), (33, 64, 64, 64), (128, 64, 64, 64)])
+
+
+@_fuse_shapes
+def test_dense_fwd_drop_matches_pair_bitwise(B, H, D, E):
+    """dense_fwd_drop == dense_fwd + hash_dropout"""
     from sat_amd import _C
     torch.manual_seed(33)
-    B, H, D, E, A = 32, 512, 512, 512, 512
-    V_ = 1000
-    I = D + E
-    W = H + D + E
-    seed = torch.tensor(777, dtype=torch.int64, device=DEV)
-    p_fc, p_lstm, s = 0.5, 0.3, 48
-
-    # dense_fwd_drop == dense_fwd + hash_dropout
+    A = 512
+    seed = _fuse_seed()
     x = _bf(torch.randn(B, A))
     w = _bf(torch.randn(H, A) * 0.05)
-    eb = torch.empty(0, dtype=torch.bfloat16, device=DEV)
-    y1 = _C.dense_fwd_drop(x, w, seed, p_fc, s + 1)
-    y2 = _C.hash_dropout(_C.dense_fwd(x, w, eb, 0), seed, p_fc, s + 1)
+    y1 = _C.dense_fwd_drop(x, w, seed, _P_FC, _SALT + 1)
+    y2 = _C.hash_dropout(_C.dense_fwd(x, w, _empty_bf(0), 0), seed,
+                         _P_FC, _SALT + 1)
     assert torch.equal(y1, y2)
 
-    # dense_dx_fuse == dense_fwd + dx_fuse
+
+def test_dense_fwd_drop_single_split_bitwise():
+    """K=32 leaves the skinny plan at splitk == 1: the fused entry point
+    still runs the GEMM in slab mode (one slab) under its own epilogue."""
+    from sat_amd import _C
+    torch.manual_seed(34)
+    seed = _fuse_seed()
+    x = _bf(torch.randn(32, 32))
+    w = _bf(torch.randn(72, 32) * 0.05)
+    y1 = _C.dense_fwd_drop(x, w, seed, _P_FC, _SALT + 1)
+    y2 = _C.hash_dropout(_C.dense_fwd(x, w, _empty_bf(0), 0), seed,
+                         _P_FC, _SALT + 1)
+    assert torch.equal(y1, y2)
+
+
+@_fuse_shapes
+def test_dense_dx_fuse_matches_pair(B, H, D, E):
+    """dense_dx_fuse == dense_fwd + dx_fuse"""
+    from sat_amd import _C
+    torch.manual_seed(35)
+    I = D + E
+    seed = _fuse_seed()
     dgates = _bf(torch.randn(B, 4 * H) * 0.1)
     wl_t = _bf(torch.randn(I + H, 4 * H) * 0.05)
     dpool_dec = _bf(torch.randn(B, D))
     demb_dec = _bf(torch.randn(B, E))
-    demb1 = torch.empty(B, E, dtype=torch.bfloat16, device=DEV)
-    demb2 = torch.empty(B, E, dtype=torch.bfloat16, device=DEV)
+    demb1 = _empty_bf(B, E)
+    demb2 = _empty_bf(B, E)
     dp1, ds1 = _C.dense_dx_fuse(dgates, wl_t, dpool_dec, demb_dec,
-                                seed, demb1, p_lstm, s + 3, D, E, H)
-    dxh = _C.dense_fwd(dgates, wl_t, eb, 0)
+                                seed, demb1, _P_LSTM, _SALT + 3, D, E, H)
+    dxh = _C.dense_fwd(dgates, wl_t, _empty_bf(0), 0)
     dp2, ds2 = _C.dx_fuse(dxh, dpool_dec, demb_dec, seed, demb2,
-                          p_lstm, s + 3, H)
+                          _P_LSTM, _SALT + 3, H)
     _one_ulp(dp1, dp2)       # pair rounds dxh to bf16 first
     _one_ulp(ds1, ds2)
     _one_ulp(demb1, demb2)
 
-    # dense_lstm_expand_fwd == dense_lstm_fwd + expand_fuse
+
+@_fuse_shapes
+def test_dense_lstm_expand_fwd_matches_pair(B, H, D, E):
+    """dense_lstm_expand_fwd == dense_lstm_fwd + expand_fuse"""
+    from sat_amd import _C
+    torch.manual_seed(36)
+    V_ = 1000
+    I = D + E
+    W = H + D + E
+    seed = _fuse_seed()
     xh = _bf(torch.randn(B, I + H) * 0.1)
     wl = _bf(torch.randn(4 * H, I + H) * 0.05)
     bl = _bf(torch.zeros(4 * H))
@@ -587,53 +638,65 @@ def test_fused_kernels_match_their_unfused_pairs_bitwise():
     pooled = _bf(torch.randn(B, D))
     table = _bf(torch.randn(V_, E))
     ids = torch.randint(0, V_, (B,), device=DEV)
-    e1 = torch.empty(B, W, dtype=torch.bfloat16, device=DEV)
-    e2 = torch.empty(B, W, dtype=torch.bfloat16, device=DEV)
-    od1 = torch.empty(B, H, dtype=torch.bfloat16, device=DEV)
-    od2 = torch.empty(B, H, dtype=torch.bfloat16, device=DEV)
+    e1, e2 = _empty_bf(B, W), _empty_bf(B, W)
+    od1, od2 = _empty_bf(B, H), _empty_bf(B, H)
     g1, c1, sth1 = _C.dense_lstm_expand_fwd(
         xh, wl, bl, cprev, pooled, table, ids, seed, e1, od1,
-        1.0, p_lstm, p_fc, s)
+        1.0, _P_LSTM, _P_FC, _SALT)
     g2, h2, c2 = _C.dense_lstm_fwd(xh, wl, bl, cprev, 1.0)
     _out2, sth2 = _C.expand_fuse(h2, pooled, table, ids, seed, e2, od2,
-                                 p_lstm, p_fc, s)
+                                 _P_LSTM, _P_FC, _SALT)
     assert torch.equal(g1, g2)   # identical fp32 math, rounded once
     assert torch.equal(c1, c2)
     _one_ulp(sth1, sth2)         # pair rounds h_raw to bf16 first
     _one_ulp(e1, e2)
     _one_ulp(od1, od2)
 
-    # dexp_lstm_bwd == dexp_fuse + lstm_pointwise_bwd_out
+
+@_fuse_shapes
+def test_dexp_lstm_bwd_matches_pair(B, H, D, E):
+    """dexp_lstm_bwd == dexp_fuse + lstm_pointwise_bwd_out"""
+    from sat_amd import _C
+    torch.manual_seed(37)
+    W = H + D + E
+    seed = _fuse_seed()
+    gates = _bf(torch.randn(B, 4 * H))
+    cprev = _bf(torch.randn(B, H))
     dexpd = _bf(torch.randn(B, W) * 0.1)
     doc = _bf(torch.randn(B, H) * 0.1)
     dsc = _bf(torch.randn(B, H) * 0.1)
     dcc = _bf(torch.randn(B, H) * 0.1)
-    DG1 = torch.empty(B, 4 * H, dtype=torch.bfloat16, device=DEV)
-    DG2 = torch.empty(B, 4 * H, dtype=torch.bfloat16, device=DEV)
+    DG1 = _empty_bf(B, 4 * H)
+    DG2 = _empty_bf(B, 4 * H)
     dcp1, dpd1, ded1 = _C.dexp_lstm_bwd(
-        dexpd, doc, dsc, seed, g2, cprev, dcc, DG1,
-        p_fc, p_lstm, s, D, E, 1.0)
-    dh2, dpd2, ded2 = _C.dexp_fuse(dexpd, doc, dsc, seed, p_fc, p_lstm,
-                                   s, D, E)
-    dg2, dcp2 = _C.lstm_pointwise_bwd_out(g2, cprev, dh2, dcc, 1.0, DG2)
+        dexpd, doc, dsc, seed, gates, cprev, dcc, DG1,
+        _P_FC, _P_LSTM, _SALT, D, E, 1.0)
+    dh2, dpd2, ded2 = _C.dexp_fuse(dexpd, doc, dsc, seed, _P_FC, _P_LSTM,
+                                   _SALT, D, E)
+    dg2, dcp2 = _C.lstm_pointwise_bwd_out(gates, cprev, dh2, dcc, 1.0, DG2)
     _one_ulp(DG1, DG2)           # pair rounds dh_raw to bf16 first
     _one_ulp(dcp1, dcp2)
     assert torch.equal(dpd1, dpd2)   # same single-rounding math
     assert torch.equal(ded1, ded2)
 
-    # attn_scores_bwd_tanh == attn_scores_bwd_acc + act_bwd_out
-    L = 196
+
+def test_attn_scores_bwd_tanh_matches_pair():
+    """attn_scores_bwd_tanh == attn_scores_bwd_acc + act_bwd_out"""
+    from sat_amd import _C
+    torch.manual_seed(38)
+    B, A, L = 32, 512, 196
+    seed = _fuse_seed()
     t1y = _bf(torch.tanh(torch.randn(B * L, A)))
     tdrop = _bf(torch.randn(B * L, A))
     dlog = torch.randn(B, L, device=DEV)
     vvec = _bf(torch.randn(A) * 0.05)
     dv1 = torch.zeros(A, dtype=torch.float32, device=DEV)
     dv2 = torch.zeros(A, dtype=torch.float32, device=DEV)
-    out1 = torch.empty(B * L, A, dtype=torch.bfloat16, device=DEV)
+    out1 = _empty_bf(B * L, A)
     _d1, dt2a, _ = _C.attn_scores_bwd_tanh(
-        tdrop, vvec, dlog, seed, p_fc, s + 2, L, dv1, t1y, out1)
+        tdrop, vvec, dlog, seed, _P_FC, _SALT + 2, L, dv1, t1y, out1)
     dt1b, dt2b, _ = _C.attn_scores_bwd_acc(
-        tdrop, vvec, dlog, seed, p_fc, s + 2, L, dv2)
+        tdrop, vvec, dlog, seed, _P_FC, _SALT + 2, L, dv2)
     out2 = torch.empty_like(out1)
     _C.act_bwd_out(dt1b, t1y, 1, out2)
     _one_ulp(out1, out2)         # pair rounds dt1 to bf16 first
