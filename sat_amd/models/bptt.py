@@ -35,6 +35,11 @@ from sat_amd import _C
 
 ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2
 
+# The B <= 128 step chain with its epilogue / elementwise launches folded
+# into their producers and consumers (docs/KERNELS.md).  False runs the
+# same steps launch by launch; tests compare the two.
+CHAIN_FUSION = True
+
 
 def _drop(x, seed, p, salt):
     if p <= 0.0:
@@ -107,10 +112,17 @@ class DecoderCoreBPTT(torch.autograd.Function):
         empty_b = _EMPTY_B(dev)
         fuse_small = (B <= 128 and (I + H) % 32 == 0
                       and (H + D + E) % 32 == 0)
+        chain = fuse_small and CHAIN_FUSION
 
         # attend input for step 0 (later steps' come fused out of
         # expand_fuse at step t-1)
         _C.hash_dropout_out(init_output, seed, p_fc, 1, ODROP[0:B])
+        if chain:
+            # embedding + state columns of XH[0]; inside the loop step t's
+            # gates epilogue writes them for step t+1, and the pooled
+            # columns come straight out of the attention pool
+            _C.lstm_in_tail(emb_c, last_word, state_h, seed, p_lstm, 3,
+                            XH[0:B], D)
 
         for t in range(T):
             s = t * 16
@@ -121,13 +133,23 @@ class DecoderCoreBPTT(torch.autograd.Function):
             t2 = _C.dense_fwd(ODROP[sl], w1b_c, b1b_c, ACT_TANH)
             tdrop, att_logits = _C.attn_scores_fused(
                 t1, t2, v_c, seed, p_fc, s + 2, L)
-            alpha, pooled = _C.attn_pool_fwd(contexts, att_logits)
-
-            _C.lstm_in_fuse(pooled, emb_c, last_word, state_h, seed,
-                            p_lstm, s + 3, XH[sl])
+            if chain:
+                alpha, pooled = _C.attn_pool_fwd_xh(
+                    contexts, att_logits, seed, p_lstm, s + 3, XH[sl], I)
+            else:
+                alpha, pooled = _C.attn_pool_fwd(contexts, att_logits)
+                _C.lstm_in_fuse(pooled, emb_c, last_word, state_h, seed,
+                                p_lstm, s + 3, XH[sl])
             od_next = ODROP[(t + 1) * B:(t + 2) * B] if t + 1 < T \
                 else empty_b
-            if fuse_small:
+            if chain:
+                xh_next = XH[(t + 1) * B:(t + 2) * B] if t + 1 < T \
+                    else empty_b
+                gates, c_new, sth_t = _C.dense_lstm_expand_xh_fwd(
+                    XH[sl], wl_c, bl_c, memory, pooled, emb_c,
+                    last_word, seed, EXPD[sl], od_next,
+                    1.0, p_lstm, p_fc, s, labels_cat[sl], xh_next)
+            elif fuse_small:
                 # gates GEMM -> gate math + expand scatter in ONE
                 # epilogue (h_raw / out_t never touch HBM)
                 gates, c_new, sth_t = _C.dense_lstm_expand_fwd(
@@ -166,6 +188,7 @@ class DecoderCoreBPTT(torch.autograd.Function):
         ctx_ag.p_fc = p_fc
         ctx_ag.p_lstm = p_lstm
         ctx_ag.train_cnn = train_cnn
+        ctx_ag.chain = chain
         return EXPD, attn_acc
 
     @staticmethod
@@ -198,6 +221,13 @@ class DecoderCoreBPTT(torch.autograd.Function):
         dv_acc = torch.zeros_like(v, dtype=torch.float32)
         dctx_acc = torch.zeros_like(contexts) if need_dctx else None
 
+        chain = ctx_ag.chain
+        # one zeroed dt2 accumulator for all T steps (the scores kernel
+        # atomically adds into its step's slice)
+        DT2 = torch.zeros(T, B, A, dtype=torch.float32, device=dev) \
+            if chain else None
+        carry_slabs, carry_salt = None, 0
+
         d_out_carry = torch.zeros(B, H, dtype=torch.bfloat16, device=dev)
         d_sth_carry = torch.zeros(B, H, dtype=torch.bfloat16, device=dev)
         dc_carry = torch.zeros(B, H, dtype=torch.bfloat16, device=dev)
@@ -207,10 +237,19 @@ class DecoderCoreBPTT(torch.autograd.Function):
             sl = slice(t * B, (t + 1) * B)
             # dexp scatter + LSTM pointwise backward fused: dh_raw
             # stays in registers inside the one kernel
-            dc_prev, dpool_dec, demb_dec = _C.dexp_lstm_bwd(
-                d_expd[sl], d_out_carry, d_sth_carry, seed,
-                gates_l[t], cprev_l[t], dc_carry, DG[sl],
-                p_fc, p_lstm, s, D, E, 1.0)
+            if carry_slabs is not None:
+                # d_out_carry still as the dodrop GEMM's split-K slabs:
+                # their epilogue (sum, ODROP mask of the producing step,
+                # bf16 rounding) runs inside this kernel
+                dc_prev, dpool_dec, demb_dec = _C.dexp_lstm_bwd_slabs(
+                    d_expd[sl], carry_slabs, carry_salt, d_sth_carry,
+                    seed, gates_l[t], cprev_l[t], dc_carry, DG[sl],
+                    p_fc, p_lstm, s, D, E, 1.0)
+            else:
+                dc_prev, dpool_dec, demb_dec = _C.dexp_lstm_bwd(
+                    d_expd[sl], d_out_carry, d_sth_carry, seed,
+                    gates_l[t], cprev_l[t], dc_carry, DG[sl],
+                    p_fc, p_lstm, s, D, E, 1.0)
             dgates = DG[sl]
             if B <= 128:
                 # dxh GEMM + the dx scatter in one epilogue
@@ -235,20 +274,39 @@ class DecoderCoreBPTT(torch.autograd.Function):
             # dt1 tanh-backward fused into the scores kernel, written
             # straight into the DPRE1A slab (one launch + no dt1
             # round-trip instead of scores_bwd + act_bwd_out)
-            _dt1, dt2f, _dv = _C.attn_scores_bwd_tanh(
-                tdrops[t], v, dlog_att, seed, p_fc, s + 2, L, dv_acc,
-                t1s[t], DPRE1A[sl_a])
+            if chain:
+                _dt1, dt2f, _dv = _C.attn_scores_bwd_step(
+                    tdrops[t], v, dlog_att, seed, p_fc, s + 2, L, dv_acc,
+                    t1s[t], DPRE1A[sl_a], DT2[t])
+            else:
+                _dt1, dt2f, _dv = _C.attn_scores_bwd_tanh(
+                    tdrops[t], v, dlog_att, seed, p_fc, s + 2, L, dv_acc,
+                    t1s[t], DPRE1A[sl_a])
 
-            _C.act_bwd_f32_out(dt2f, t2s[t], ACT_TANH, DPRE1B[sl])
-            # dodrop GEMM with the ODROP mask (salt s+1) regenerated in
-            # the split-K epilogue — one launch instead of GEMM+dropout
-            d_out_carry = _C.dense_fwd_drop(DPRE1B[sl], w1b_t, seed,
-                                            p_fc, s + 1)
+            if chain:
+                # dodrop GEMM with the tanh backward of dt2 built in its
+                # A-operand load (DPRE1B[t] stored on the side); its
+                # split-K slabs go to the next iteration as they are
+                carry_slabs = _C.dense_tanhbwd_slabs(dt2f, t2s[t], w1b_t,
+                                                     DPRE1B[sl])
+                carry_salt = s + 1
+            else:
+                _C.act_bwd_f32_out(dt2f, t2s[t], ACT_TANH, DPRE1B[sl])
+                # dodrop GEMM with the ODROP mask (salt s+1) regenerated
+                # in the split-K epilogue — one launch instead of
+                # GEMM+dropout
+                d_out_carry = _C.dense_fwd_drop(DPRE1B[sl], w1b_t, seed,
+                                                p_fc, s + 1)
 
             if need_dctx:
                 dcd = DPRE1A[sl_a].matmul(w1a)
                 dctx_acc += _drop(dcd, seed, p_fc, s + 0) \
                     .reshape(B, L, D)
+
+        if carry_slabs is not None:
+            # the last carry is needed as a tensor (d_init_output)
+            d_out_carry = _C.slab_epilogue_drop(carry_slabs, seed, p_fc,
+                                                carry_salt)
 
         # ---- batched weight grads ----
         if CDROP is not None:

@@ -129,6 +129,33 @@ void adam_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                double steps_per_decay, double b1, double b2, double eps,
                double clip, at::Tensor gsq);
 
+// per-step chain fusions of the decoder BPTT (sat_amd/models/bptt.py)
+std::vector<at::Tensor> attn_scores_bwd_step(
+    at::Tensor tdrop, at::Tensor v, at::Tensor dlogits, at::Tensor seed,
+    double p, int64_t salt, int64_t L, at::Tensor dv_acc, at::Tensor t1y,
+    at::Tensor dt1_out, at::Tensor dt2_out);
+std::vector<at::Tensor> attn_pool_fwd_xh(at::Tensor ctx, at::Tensor logits,
+                                         at::Tensor seed, double p,
+                                         int64_t salt, at::Tensor xh,
+                                         int64_t I);
+void lstm_in_tail(at::Tensor table, at::Tensor ids, at::Tensor sth,
+                  at::Tensor seed, double p, int64_t salt, at::Tensor xh,
+                  int64_t D);
+std::vector<at::Tensor> dense_lstm_expand_xh_fwd(
+    at::Tensor xh, at::Tensor wl, at::Tensor bl, at::Tensor c_prev,
+    at::Tensor pooled, at::Tensor table, at::Tensor ids, at::Tensor seed,
+    at::Tensor expdrop, at::Tensor od_next, double fb, double p_lstm,
+    double p_fc, int64_t s, at::Tensor next_ids, at::Tensor xh_next);
+at::Tensor dense_tanhbwd_slabs(at::Tensor dy, at::Tensor y, at::Tensor w,
+                               at::Tensor dpre_out);
+at::Tensor slab_epilogue_drop(at::Tensor yf, at::Tensor seed, double p,
+                              int64_t salt);
+std::vector<at::Tensor> dexp_lstm_bwd_slabs(
+    at::Tensor dexpd, at::Tensor carry_slabs, int64_t carry_salt,
+    at::Tensor d_sth_carry, at::Tensor seed, at::Tensor gates,
+    at::Tensor c_prev, at::Tensor dc, at::Tensor dgates_out, double p_fc,
+    double p_lstm, int64_t s, int64_t D, int64_t E, double fb);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("dense_fwd", &dense_fwd, "MFMA GEMM + bias/act (bf16)");
     m.def("dense_fwd_drop", &dense_fwd_drop,
@@ -184,4 +211,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sq_norm_mt", &sq_norm_mt);
     m.def("adam_step_mt", &adam_step_mt);
     m.def("adam_step", &adam_step);
+    m.def("attn_scores_bwd_step", &attn_scores_bwd_step,
+          "attn_scores_bwd_tanh into a caller-zeroed dt2 slice");
+    m.def("attn_pool_fwd_xh", &attn_pool_fwd_xh,
+          "attention pool that also writes the dropped pooled columns "
+          "of the LSTM input");
+    m.def("lstm_in_tail", &lstm_in_tail,
+          "embedding + state columns of the LSTM input (step 0)");
+    m.def("dense_lstm_expand_xh_fwd", &dense_lstm_expand_xh_fwd,
+          "dense_lstm_expand_fwd that also lays down the next step's "
+          "embedding + state LSTM-input columns");
+    m.def("dense_tanhbwd_slabs", &dense_tanhbwd_slabs,
+          "split-K slabs of (dy * (1 - y^2)) @ w^T, tanh backward built "
+          "in the A-operand load");
+    m.def("slab_epilogue_drop", &slab_epilogue_drop,
+          "bf16(sum of split-K slabs * dropout mask)");
+    m.def("dexp_lstm_bwd_slabs", &dexp_lstm_bwd_slabs,
+          "dexp_lstm_bwd taking d_out_carry as split-K slabs + salt");
 }

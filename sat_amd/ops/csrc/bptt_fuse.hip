@@ -23,6 +23,8 @@ __global__ void lstm_in_fuse_kernel(const bf16* __restrict__ pooled,
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)B * W) return;
     int b = idx / W, j = idx % W;
+    // pooled == null: the pooled columns are another kernel's to write
+    if (j < D && pooled == nullptr) return;
     float val;
     if (j < I) {
         val = (j < D) ? bf2f(pooled[(int64_t)b * D + j])
@@ -49,6 +51,28 @@ void lstm_in_fuse(at::Tensor pooled, at::Tensor table, at::Tensor ids,
                        (const bf16*)sth.data_ptr(),
                        (const int64_t*)seed.data_ptr(),
                        (bf16*)xh.data_ptr(), B, D, E, H,
+                       (float)p, (int)salt);
+    HIP_OK(hipGetLastError());
+}
+
+// the embedding and state columns of xh alone (columns [D, D+E+H)): the
+// pooled columns come from attn_pool_fwd_xh.  Inside the step loop the
+// previous step's gates epilogue writes these; this is step 0's launch.
+void lstm_in_tail(at::Tensor table, at::Tensor ids, at::Tensor sth,
+                  at::Tensor seed, double p, int64_t salt, at::Tensor xh,
+                  int64_t D) {
+    int B = sth.size(0), E = table.size(1), H = sth.size(1);
+    TORCH_CHECK(xh.is_contiguous() && xh.numel() == (int64_t)B * (D + E + H)
+                && ids.numel() == B);
+    int64_t n = (int64_t)B * (D + E + H);
+    hipStream_t s = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(lstm_in_fuse_kernel, dim3(cdiv(n, 256)), dim3(256),
+                       0, s, (const bf16*)nullptr,
+                       (const bf16*)table.data_ptr(),
+                       (const int64_t*)ids.data_ptr(),
+                       (const bf16*)sth.data_ptr(),
+                       (const int64_t*)seed.data_ptr(),
+                       (bf16*)xh.data_ptr(), B, (int)D, E, H,
                        (float)p, (int)salt);
     HIP_OK(hipGetLastError());
 }
@@ -400,7 +424,11 @@ at::Tensor hash_dropout_slabs(at::Tensor x, at::Tensor seed, double p,
 
 // ---- dexp_fuse + LSTM pointwise backward in ONE launch: the H-range
 // threads continue straight into the gate math (dh_raw never touches
-// HBM); D/E-range threads do the dexp scatter as before ----
+// HBM); D/E-range threads do the dexp scatter as before.
+// d_out_carry arrives either as bf16, or (carry_slabs != null) as the
+// fp32 split-K slabs of the producing step's dodrop GEMM, finished here
+// exactly as skinny_epilogue_drop_kernel would: sum, ODROP mask of
+// carry_salt, one bf16 rounding ----
 
 __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
                                      const bf16* __restrict__ d_out_carry,
@@ -415,7 +443,9 @@ __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
                                      bf16* __restrict__ demb_dec,
                                      int B, int H, int D, int E,
                                      float p_fc, float p_lstm, int s,
-                                     float fb) {
+                                     float fb,
+                                     const float* __restrict__ carry_slabs,
+                                     int carry_splitk, int carry_salt) {
     const uint32_t seed = (uint32_t)(*seed_p);
     const int W = H + D + E;
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -425,7 +455,16 @@ __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
         * drop_scale(seed, s + 6, (uint32_t)(b * W + j), p_fc);
     if (j < H) {
         uint32_t hidx = (uint32_t)(b * H + j);
-        float dout = dexp + bf2f(d_out_carry[(int64_t)b * H + j]);
+        float doc;
+        if (carry_slabs != nullptr) {
+            float v = sum_slabs(carry_slabs, (int64_t)B * H,
+                                (int64_t)b * H + j, carry_splitk);
+            v *= drop_scale(seed, carry_salt, hidx, p_fc);
+            doc = bf2f(f2bf(v));
+        } else {
+            doc = bf2f(d_out_carry[(int64_t)b * H + j]);
+        }
+        float dout = dexp + doc;
         float dhv = dout * drop_scale(seed, s + 4, hidx, p_lstm)
             + bf2f(d_sth_carry[(int64_t)b * H + j])
             * drop_scale(seed, s + 5, hidx, p_lstm);
@@ -447,17 +486,14 @@ __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
     }
 }
 
-std::vector<at::Tensor> dexp_lstm_bwd(at::Tensor dexpd,
-                                      at::Tensor d_out_carry,
-                                      at::Tensor d_sth_carry,
-                                      at::Tensor seed, at::Tensor gates,
-                                      at::Tensor c_prev, at::Tensor dc,
-                                      at::Tensor dgates_out,
-                                      double p_fc, double p_lstm,
-                                      int64_t s, int64_t D, int64_t E,
-                                      double fb) {
+static std::vector<at::Tensor> dexp_lstm_bwd_impl(
+        at::Tensor dexpd, const bf16* carry_ptr, const float* slab_ptr,
+        int carry_splitk, int64_t carry_salt, at::Tensor d_sth_carry,
+        at::Tensor seed, at::Tensor gates, at::Tensor c_prev,
+        at::Tensor dc, at::Tensor dgates_out, double p_fc, double p_lstm,
+        int64_t s, int64_t D, int64_t E, double fb) {
     CHECK_GPU(dexpd); CHECK_BF16(dexpd);
-    int B = d_out_carry.size(0), H = d_out_carry.size(1);
+    int B = d_sth_carry.size(0), H = d_sth_carry.size(1);
     TORCH_CHECK(dexpd.numel() == (int64_t)B * (H + D + E));
     TORCH_CHECK(dgates_out.numel() == (int64_t)B * 4 * H);
     auto dc_prev = at::empty({B, H}, dexpd.options());
@@ -470,8 +506,7 @@ std::vector<at::Tensor> dexp_lstm_bwd(at::Tensor dexpd,
     hipStream_t st = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(dexp_lstm_bwd_kernel, dim3(cdiv(n, 256)),
                        dim3(256), 0, st,
-                       (const bf16*)dexpd.data_ptr(),
-                       (const bf16*)d_out_carry.data_ptr(),
+                       (const bf16*)dexpd.data_ptr(), carry_ptr,
                        (const bf16*)d_sth_carry.data_ptr(),
                        (const int64_t*)seed.data_ptr(),
                        (const bf16*)gates.data_ptr(),
@@ -481,7 +516,51 @@ std::vector<at::Tensor> dexp_lstm_bwd(at::Tensor dexpd,
                        (bf16*)dpool_dec.data_ptr(),
                        (bf16*)demb_dec.data_ptr(),
                        B, H, (int)D, (int)E,
-                       (float)p_fc, (float)p_lstm, (int)s, (float)fb);
+                       (float)p_fc, (float)p_lstm, (int)s, (float)fb,
+                       slab_ptr, carry_splitk, (int)carry_salt);
     HIP_OK(hipGetLastError());
     return {dc_prev, dpool_dec, demb_dec};
+}
+
+std::vector<at::Tensor> dexp_lstm_bwd(at::Tensor dexpd,
+                                      at::Tensor d_out_carry,
+                                      at::Tensor d_sth_carry,
+                                      at::Tensor seed, at::Tensor gates,
+                                      at::Tensor c_prev, at::Tensor dc,
+                                      at::Tensor dgates_out,
+                                      double p_fc, double p_lstm,
+                                      int64_t s, int64_t D, int64_t E,
+                                      double fb) {
+    TORCH_CHECK(d_out_carry.numel() == d_sth_carry.numel());
+    return dexp_lstm_bwd_impl(dexpd, (const bf16*)d_out_carry.data_ptr(),
+                              nullptr, 0, 0, d_sth_carry, seed, gates,
+                              c_prev, dc, dgates_out, p_fc, p_lstm, s, D,
+                              E, fb);
+}
+
+// d_out_carry taken as the [splitk, B, H] fp32 slabs of the producing
+// step's dodrop GEMM (dense_tanhbwd_slabs) and that step's ODROP salt
+std::vector<at::Tensor> dexp_lstm_bwd_slabs(at::Tensor dexpd,
+                                            at::Tensor carry_slabs,
+                                            int64_t carry_salt,
+                                            at::Tensor d_sth_carry,
+                                            at::Tensor seed,
+                                            at::Tensor gates,
+                                            at::Tensor c_prev,
+                                            at::Tensor dc,
+                                            at::Tensor dgates_out,
+                                            double p_fc, double p_lstm,
+                                            int64_t s, int64_t D,
+                                            int64_t E, double fb) {
+    CHECK_GPU(carry_slabs); CHECK_CONTIG(carry_slabs);
+    CHECK_F32(carry_slabs);
+    TORCH_CHECK(carry_slabs.dim() == 3
+                && carry_slabs.size(1) == d_sth_carry.size(0)
+                && carry_slabs.size(2) == d_sth_carry.size(1),
+                "carry slabs must be [splitk, B, H]");
+    return dexp_lstm_bwd_impl(dexpd, nullptr,
+                              (const float*)carry_slabs.data_ptr(),
+                              (int)carry_slabs.size(0), carry_salt,
+                              d_sth_carry, seed, gates, c_prev, dc,
+                              dgates_out, p_fc, p_lstm, s, D, E, fb);
 }

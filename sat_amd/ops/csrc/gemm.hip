@@ -176,16 +176,24 @@ void tiled_gemm_kernel(const bf16* __restrict__ A,    // [M,K]
 // (needs splitk == 1); otherwise block row kq stores its K-chunk's
 // partial sums into fp32 slab kq and a separate epilogue kernel combines
 // (an empty trailing chunk stores zeros).
+//
+// TANHA (slab mode, K % 32 == 0): the A operand is not read but built as
+// it loads, a = f2bf(Af * (1 - Ay^2)) from an fp32 gradient Af and the
+// bf16 tanh output Ay (what act_bwd_f32_out computes, same rounding);
+// wave 0 of the blockIdx.x == 0 blocks stores its K-chunk of it to Apre.
 // ---------------------------------------------------------------------
 
-template <int RF>
+template <int RF, bool TANHA>
 __global__ __launch_bounds__(256)
 void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
                         const bf16* __restrict__ W,   // [N,K]
                         const bf16* __restrict__ bias,
                         bf16* __restrict__ Y,         // [M,N]
                         float* __restrict__ Yf,       // [splitk,M,N] slabs
-                        int M, int N, int K, int act, int splitk) {
+                        int M, int N, int K, int act, int splitk,
+                        const float* __restrict__ Af,   // [M,K]
+                        const bf16* __restrict__ Ay,    // [M,K]
+                        bf16* __restrict__ Apre) {      // [M,K]
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int n0 = blockIdx.x * 64 + wave * 16;
@@ -223,6 +231,24 @@ void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
             for (int mi = 0; mi < RF; ++mi) {
                 bf16x8 a0 = {};
                 int ar = mi * 16 + lrow;
+                if constexpr (TANHA) {
+                    if (ar < M) {
+                        const int64_t ao = (int64_t)ar * K + kof;
+                        floatx4 g0 = *(const floatx4*)(Af + ao);
+                        floatx4 g1 = *(const floatx4*)(Af + ao + 4);
+                        bf16x8 yv = *(const bf16x8*)(Ay + ao);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            float y = bf2f(yv[e]);
+                            float g = e < 4 ? g0[e] : g1[e - 4];
+                            // y*y is exact in fp32 (bf16 operand), so
+                            // contraction cannot move this result
+                            a0[e] = f2bf(g * (1.f - y * y));
+                        }
+                        if (blockIdx.x == 0 && wave == 0)
+                            *(bf16x8*)(Apre + ao) = a0;
+                    }
+                } else
                 if (kof + 8 <= K) {
                     if (ar < M)
                         a0 = *(const bf16x8*)(A + (int64_t)ar * K + kof);
@@ -314,13 +340,49 @@ static void launch_skinny(hipStream_t stream, const at::Tensor& x,
     const int M = x.size(0), K = x.size(1), N = w.size(0);
     TORCH_CHECK(is_skinny(M, K),
                 "skinny GEMM: M <= 128 and K % 32 == 0 only");
-    auto kernel = M <= 32 ? skinny_gemm_kernel<2>
-                : M <= 64 ? skinny_gemm_kernel<4>
-                          : skinny_gemm_kernel<8>;
+    auto kernel = M <= 32 ? skinny_gemm_kernel<2, false>
+                : M <= 64 ? skinny_gemm_kernel<4, false>
+                          : skinny_gemm_kernel<8, false>;
     hipLaunchKernelGGL(kernel, dim3(plan.nblocks, plan.splitk), dim3(256),
                        0, stream, (const bf16*)x.data_ptr(),
                        (const bf16*)w.data_ptr(), bias, y, yf, M, N, K,
-                       act, plan.splitk);
+                       act, plan.splitk, (const float*)nullptr,
+                       (const bf16*)nullptr, (bf16*)nullptr);
+}
+
+// dense_fwd_drop's GEMM with act_bwd_f32_out folded into the A-operand
+// load: slabs of (dy * (1 - y^2)) @ w^T, dy [M,K] fp32, y [M,K] bf16 the
+// tanh output; dpre_out [M,K] receives the bf16 A operand (the batched
+// weight/bias gradients still read it).  The consumer finishes the slabs
+// (dexp_lstm_bwd_slabs, or slab_epilogue_drop after the loop).
+at::Tensor dense_tanhbwd_slabs(at::Tensor dy, at::Tensor y, at::Tensor w,
+                               at::Tensor dpre_out) {
+    CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_F32(dy);
+    CHECK_GPU(y); CHECK_CONTIG(y); CHECK_BF16(y);
+    CHECK_GPU(w); CHECK_CONTIG(w); CHECK_BF16(w);
+    CHECK_GPU(dpre_out); CHECK_CONTIG(dpre_out); CHECK_BF16(dpre_out);
+    TORCH_CHECK(dy.dim() == 2 && w.dim() == 2);
+    const int M = dy.size(0), K = dy.size(1), N = w.size(0);
+    TORCH_CHECK(w.size(1) == K && y.numel() == dy.numel()
+                && dpre_out.numel() == dy.numel(), "shape mismatch");
+    TORCH_CHECK(is_skinny(M, K),
+                "skinny GEMM: M <= 128 and K % 32 == 0 only");
+    SkinnyPlan plan = skinny_plan(N, K);
+    auto yf = at::empty({plan.splitk, M, N}, dy.options());
+    auto kernel = M <= 32 ? skinny_gemm_kernel<2, true>
+                : M <= 64 ? skinny_gemm_kernel<4, true>
+                          : skinny_gemm_kernel<8, true>;
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+    hipLaunchKernelGGL(kernel, dim3(plan.nblocks, plan.splitk), dim3(256),
+                       0, stream, (const bf16*)nullptr,
+                       (const bf16*)w.data_ptr(), (const bf16*)nullptr,
+                       (bf16*)nullptr, (float*)yf.data_ptr(), M, N, K,
+                       ACT_NONE, plan.splitk,
+                       (const float*)dy.data_ptr(),
+                       (const bf16*)y.data_ptr(),
+                       (bf16*)dpre_out.data_ptr());
+    HIP_OK(hipGetLastError());
+    return yf;
 }
 
 // slab-mode skinny GEMM for entry points that bring their own epilogue:
@@ -463,6 +525,25 @@ at::Tensor dense_fwd_drop(at::Tensor x, at::Tensor w, at::Tensor seed,
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
     auto yf = skinny_slabs(stream, x, w);
     int64_t n = M * N;
+    hipLaunchKernelGGL(skinny_epilogue_drop_kernel,
+                       dim3(cdiv(n, 256)), dim3(256), 0, stream,
+                       (const float*)yf.data_ptr(), (bf16*)y.data_ptr(),
+                       (const int64_t*)seed.data_ptr(), n,
+                       (int)yf.size(0), (float)p, (int)salt);
+    HIP_OK(hipGetLastError());
+    return y;
+}
+
+// the drop epilogue alone, over slabs some other entry point produced:
+// y = bf16(sum_slabs * dropout mask(salt))
+at::Tensor slab_epilogue_drop(at::Tensor yf, at::Tensor seed, double p,
+                              int64_t salt) {
+    CHECK_GPU(yf); CHECK_CONTIG(yf); CHECK_F32(yf);
+    TORCH_CHECK(yf.dim() == 3, "slabs must be [splitk, M, N]");
+    auto y = at::empty({yf.size(1), yf.size(2)},
+                       yf.options().dtype(at::kBFloat16));
+    int64_t n = y.numel();
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(skinny_epilogue_drop_kernel,
                        dim3(cdiv(n, 256)), dim3(256), 0, stream,
                        (const float*)yf.data_ptr(), (bf16*)y.data_ptr(),
@@ -728,6 +809,12 @@ std::vector<at::Tensor> dense_dx_fuse(at::Tensor dgates, at::Tensor wl_t,
 // pooled / embedding-gather parts of the expand row.  Replaces
 // skinny_epi_lstm + expand_fuse.  Dropout salts identical to the pair
 // it replaces (s+4 out, s+5 state, s+6 expand, s+17 next attend).
+//
+// xh_next != null: the threads also lay down the NEXT step's LSTM input
+// row where they already hold its values — H-range threads the state_h
+// columns [I, I+H), E-range threads dropout(table[next_ids], salt s+16+3)
+// into [D, I) — so no lstm_in_fuse launch sits between the steps (the
+// pooled columns [0, D) come from the next step's attn_pool_fwd_xh).
 // ---------------------------------------------------------------------
 
 __global__ void skinny_epi_lstm_expand_kernel(
@@ -741,9 +828,12 @@ __global__ void skinny_epi_lstm_expand_kernel(
         bf16* __restrict__ sth_t, bf16* __restrict__ expdrop,
         bf16* __restrict__ od_next,
         int B, int H, int D, int E, int splitk,
-        float fb, float p_lstm, float p_fc, int s) {
+        float fb, float p_lstm, float p_fc, int s,
+        const int64_t* __restrict__ next_ids,
+        bf16* __restrict__ xh_next) {
     const uint32_t seed = (uint32_t)(*seed_p);
     const int W = H + D + E;
+    const int I = D + E;
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)B * W) return;
     int b = idx / W, j = idx % W;
@@ -755,8 +845,10 @@ __global__ void skinny_epi_lstm_expand_kernel(
         c_out[(int64_t)b * H + j] = f2bf(cn);
         uint32_t hidx = (uint32_t)(b * H + j);
         float ot = h * drop_scale(seed, s + 4, hidx, p_lstm);
-        sth_t[(int64_t)b * H + j] =
-            f2bf(h * drop_scale(seed, s + 5, hidx, p_lstm));
+        bf16 sth = f2bf(h * drop_scale(seed, s + 5, hidx, p_lstm));
+        sth_t[(int64_t)b * H + j] = sth;
+        if (xh_next != nullptr)
+            xh_next[(int64_t)b * W + I + j] = sth;
         if (od_next != nullptr)
             od_next[(int64_t)b * H + j] =
                 f2bf(ot * drop_scale(seed, s + 16 + 1, hidx, p_fc));
@@ -764,17 +856,24 @@ __global__ void skinny_epi_lstm_expand_kernel(
     } else if (j < H + D) {
         val = bf2f(pooled[(int64_t)b * D + (j - H)]);
     } else {
-        val = bf2f(table[ids[b] * E + (j - H - D)]);
+        int e = j - H - D;
+        val = bf2f(table[ids[b] * E + e]);
+        if (xh_next != nullptr)
+            xh_next[(int64_t)b * W + D + e] =
+                f2bf(bf2f(table[next_ids[b] * E + e])
+                     * drop_scale(seed, s + 16 + 3,
+                                  (uint32_t)(b * I + D + e), p_lstm));
     }
     expdrop[idx] = f2bf(val * drop_scale(seed, s + 6,
                                          (uint32_t)(b * W + j), p_fc));
 }
 
-std::vector<at::Tensor> dense_lstm_expand_fwd(
+static std::vector<at::Tensor> dense_lstm_expand_impl(
         at::Tensor xh, at::Tensor wl, at::Tensor bl, at::Tensor c_prev,
         at::Tensor pooled, at::Tensor table, at::Tensor ids,
         at::Tensor seed, at::Tensor expdrop, at::Tensor od_next,
-        double fb, double p_lstm, double p_fc, int64_t s) {
+        double fb, double p_lstm, double p_fc, int64_t s,
+        const int64_t* next_ids_ptr, bf16* xh_next_ptr) {
     int64_t M = xh.size(0), N = wl.size(0);
     int B = c_prev.size(0), H = c_prev.size(1);
     int D = pooled.size(1), E = table.size(1);
@@ -804,7 +903,44 @@ std::vector<at::Tensor> dense_lstm_expand_fwd(
                        (bf16*)sth_t.data_ptr(),
                        (bf16*)expdrop.data_ptr(), od_ptr,
                        B, H, D, E, (int)yf.size(0),
-                       (float)fb, (float)p_lstm, (float)p_fc, (int)s);
+                       (float)fb, (float)p_lstm, (float)p_fc, (int)s,
+                       next_ids_ptr, xh_next_ptr);
     HIP_OK(hipGetLastError());
     return {gates, c_out, sth_t};
+}
+
+std::vector<at::Tensor> dense_lstm_expand_fwd(
+        at::Tensor xh, at::Tensor wl, at::Tensor bl, at::Tensor c_prev,
+        at::Tensor pooled, at::Tensor table, at::Tensor ids,
+        at::Tensor seed, at::Tensor expdrop, at::Tensor od_next,
+        double fb, double p_lstm, double p_fc, int64_t s) {
+    return dense_lstm_expand_impl(xh, wl, bl, c_prev, pooled, table, ids,
+                                  seed, expdrop, od_next, fb, p_lstm, p_fc,
+                                  s, nullptr, nullptr);
+}
+
+// dense_lstm_expand_fwd that also writes the embedding (next_ids) and
+// state columns of the next step's LSTM input rows xh_next [B, D+E+H];
+// an empty xh_next (the last step) writes none
+std::vector<at::Tensor> dense_lstm_expand_xh_fwd(
+        at::Tensor xh, at::Tensor wl, at::Tensor bl, at::Tensor c_prev,
+        at::Tensor pooled, at::Tensor table, at::Tensor ids,
+        at::Tensor seed, at::Tensor expdrop, at::Tensor od_next,
+        double fb, double p_lstm, double p_fc, int64_t s,
+        at::Tensor next_ids, at::Tensor xh_next) {
+    const int64_t* nid = nullptr;
+    bf16* xn = nullptr;
+    if (xh_next.defined() && xh_next.numel() > 0) {
+        CHECK_GPU(xh_next); CHECK_CONTIG(xh_next); CHECK_BF16(xh_next);
+        CHECK_GPU(next_ids); CHECK_CONTIG(next_ids);
+        TORCH_CHECK(next_ids.scalar_type() == at::kLong
+                    && next_ids.numel() == c_prev.size(0));
+        TORCH_CHECK(xh_next.numel() == c_prev.size(0)
+                    * (c_prev.size(1) + pooled.size(1) + table.size(1)));
+        nid = (const int64_t*)next_ids.data_ptr();
+        xn = (bf16*)xh_next.data_ptr();
+    }
+    return dense_lstm_expand_impl(xh, wl, bl, c_prev, pooled, table, ids,
+                                  seed, expdrop, od_next, fb, p_lstm, p_fc,
+                                  s, nid, xn);
 }

@@ -318,67 +318,6 @@ __global__ void attn_pool_bwd_p2_kernel(
     }
 }
 
-// both phases in one block per image: per-row dots s_l (4 waves strided
-// over L) land in LDS, then the softmax-Jacobian combine — removes the
-// p2 launch and the sbuf HBM round trip from the reverse-loop chain
-__global__ void attn_pool_bwd_fused_kernel(
-        const bf16* __restrict__ ctx, const float* __restrict__ alpha,
-        const float* __restrict__ dalpha,
-        const bf16* __restrict__ dpooled, bf16* __restrict__ dctx,
-        float* __restrict__ dlogits, int L, int D) {
-    __shared__ float sL[MAX_L];
-    __shared__ float red[4];
-    int b = blockIdx.x;
-    int tid = threadIdx.x;
-    int wid = tid >> 6, lane = tid & 63;
-    const bf16* cb = ctx + (int64_t)b * L * D;
-    const bf16* dp = dpooled + (int64_t)b * D;
-
-    for (int l = wid; l < L; l += 4) {
-        float acc = 0.f;
-        float a = alpha[(int64_t)b * L + l];
-        for (int d0 = lane * 8; d0 + 8 <= D; d0 += 64 * 8) {
-            bf16x8 cv = *(const bf16x8*)(cb + (int64_t)l * D + d0);
-            bf16x8 dv = *(const bf16x8*)(dp + d0);
-            if (dctx != nullptr) {
-                bf16x8 out;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float dpe = bf2f(dv[e]);
-                    acc += bf2f(cv[e]) * dpe;
-                    out[e] = f2bf(a * dpe);
-                }
-                *(bf16x8*)(dctx + (int64_t)b * L * D + (int64_t)l * D
-                           + d0) = out;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    acc += bf2f(cv[e]) * bf2f(dv[e]);
-            }
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) sL[l] = acc;
-    }
-    __syncthreads();
-
-    float part = 0.f;
-    for (int l = tid; l < L; l += blockDim.x) {
-        float da = sL[l];
-        if (dalpha != nullptr) da += dalpha[(int64_t)b * L + l];
-        part += alpha[(int64_t)b * L + l] * da;
-    }
-    part = wave_sum(part);
-    if ((tid & 63) == 0) red[tid >> 6] = part;
-    __syncthreads();
-    float dot = red[0] + red[1] + red[2] + red[3];
-    for (int l = tid; l < L; l += blockDim.x) {
-        float da = sL[l];
-        if (dalpha != nullptr) da += dalpha[(int64_t)b * L + l];
-        dlogits[(int64_t)b * L + l] =
-            alpha[(int64_t)b * L + l] * (da - dot);
-    }
-}
-
 std::vector<at::Tensor> attn_pool_bwd(at::Tensor ctx, at::Tensor alpha,
                                       at::Tensor dalpha, at::Tensor dpooled,
                                       bool need_dctx) {
@@ -400,10 +339,9 @@ std::vector<at::Tensor> attn_pool_bwd(at::Tensor ctx, at::Tensor alpha,
     if (dalpha.defined() && dalpha.numel() > 0)
         dalpha_ptr = (const float*)dalpha.data_ptr();
     hipStream_t s = at::cuda::getCurrentCUDAStream();
-    // NOTE: a one-block-per-image fused p1+p2 variant
-    // (attn_pool_bwd_fused_kernel above) measured SLOWER at batch 32 —
-    // it cuts the p1 grid from B*4 to B blocks on a latency-bound
-    // chain; the two-launch form stays (r02 A/B evidence).
+    // NOTE: a one-block-per-image fused p1+p2 variant measured SLOWER at
+    // batch 32 — it cuts the p1 grid from B*4 to B blocks on a
+    // latency-bound chain; the two-launch form stays (r02 A/B evidence).
     hipLaunchKernelGGL(attn_pool_bwd_p1_kernel, dim3(B, 8), dim3(256), 0, s,
                        (const bf16*)ctx.data_ptr(),
                        (const float*)alpha.data_ptr(),
@@ -493,24 +431,15 @@ __global__ void attn_scores_bwd_kernel(
     }
 }
 
-std::vector<at::Tensor> attn_scores_bwd_tanh(
+// One host path for every scores-backward entry point.  dt2_out, when
+// given, is a caller-ZEROED [B, A] fp32 slice the atomics accumulate into
+// (saves the per-call fill launch); otherwise dt2 is allocated and zeroed
+// here.
+static std::vector<at::Tensor> attn_scores_bwd_impl(
         at::Tensor tdrop, at::Tensor v, at::Tensor dlogits,
         at::Tensor seed, double p, int64_t salt, int64_t L,
-        at::Tensor dv_acc, at::Tensor t1y, at::Tensor dt1_out);
-
-std::vector<at::Tensor> attn_scores_bwd_acc(at::Tensor tdrop, at::Tensor v,
-                                            at::Tensor dlogits,
-                                            at::Tensor seed, double p,
-                                            int64_t salt, int64_t L,
-                                            at::Tensor dv_acc) {
-    return attn_scores_bwd_tanh(tdrop, v, dlogits, seed, p, salt, L,
-                                dv_acc, at::Tensor(), at::Tensor());
-}
-
-std::vector<at::Tensor> attn_scores_bwd_tanh(
-        at::Tensor tdrop, at::Tensor v, at::Tensor dlogits,
-        at::Tensor seed, double p, int64_t salt, int64_t L,
-        at::Tensor dv_acc, at::Tensor t1y, at::Tensor dt1_out) {
+        at::Tensor dv_acc, at::Tensor t1y, at::Tensor dt1_out,
+        at::Tensor dt2_out) {
     CHECK_GPU(tdrop); CHECK_CONTIG(tdrop); CHECK_BF16(tdrop);
     int rows = tdrop.size(0), A = tdrop.size(1);
     TORCH_CHECK(A % 512 == 0 && A <= 2048,
@@ -528,7 +457,14 @@ std::vector<at::Tensor> attn_scores_bwd_tanh(
         TORCH_CHECK(t1y.numel() == tdrop.numel());
         t1y_ptr = (const bf16*)t1y.data_ptr();
     }
-    auto dt2 = at::zeros({B, A}, tdrop.options().dtype(at::kFloat));
+    at::Tensor dt2;
+    if (dt2_out.defined() && dt2_out.numel() > 0) {
+        CHECK_GPU(dt2_out); CHECK_CONTIG(dt2_out); CHECK_F32(dt2_out);
+        TORCH_CHECK(dt2_out.numel() == (int64_t)B * A);
+        dt2 = dt2_out;
+    } else {
+        dt2 = at::zeros({B, A}, tdrop.options().dtype(at::kFloat));
+    }
     at::Tensor dvf;
     if (dv_acc.defined() && dv_acc.numel() > 0)
         dvf = dv_acc;   // caller-owned accumulator (atomicAdd accumulates)
@@ -558,6 +494,34 @@ std::vector<at::Tensor> attn_scores_bwd_tanh(
 #undef LAUNCH_SB
     HIP_OK(hipGetLastError());
     return {dt1, dt2, dvf};
+}
+
+std::vector<at::Tensor> attn_scores_bwd_tanh(
+        at::Tensor tdrop, at::Tensor v, at::Tensor dlogits,
+        at::Tensor seed, double p, int64_t salt, int64_t L,
+        at::Tensor dv_acc, at::Tensor t1y, at::Tensor dt1_out) {
+    return attn_scores_bwd_impl(tdrop, v, dlogits, seed, p, salt, L,
+                                dv_acc, t1y, dt1_out, at::Tensor());
+}
+
+std::vector<at::Tensor> attn_scores_bwd_acc(at::Tensor tdrop, at::Tensor v,
+                                            at::Tensor dlogits,
+                                            at::Tensor seed, double p,
+                                            int64_t salt, int64_t L,
+                                            at::Tensor dv_acc) {
+    return attn_scores_bwd_tanh(tdrop, v, dlogits, seed, p, salt, L,
+                                dv_acc, at::Tensor(), at::Tensor());
+}
+
+// the decoder reverse loop's form: dt2 accumulates into a caller-zeroed
+// slice of one [T, B, A] buffer
+std::vector<at::Tensor> attn_scores_bwd_step(
+        at::Tensor tdrop, at::Tensor v, at::Tensor dlogits,
+        at::Tensor seed, double p, int64_t salt, int64_t L,
+        at::Tensor dv_acc, at::Tensor t1y, at::Tensor dt1_out,
+        at::Tensor dt2_out) {
+    return attn_scores_bwd_impl(tdrop, v, dlogits, seed, p, salt, L,
+                                dv_acc, t1y, dt1_out, dt2_out);
 }
 
 std::vector<at::Tensor> attn_scores_bwd(at::Tensor tdrop, at::Tensor v,
@@ -651,7 +615,13 @@ __global__ void attn_pool_fused_kernel(const bf16* __restrict__ ctx,
                                        const float* __restrict__ logits,
                                        float* __restrict__ alpha,
                                        bf16* __restrict__ pooled,
-                                       int L, int D) {
+                                       int L, int D,
+                                       bf16* __restrict__ xh,
+                                       const int64_t* __restrict__ seed_p,
+                                       int xh_stride, int I, float p,
+                                       int salt) {
+    // xh != null: the bf16 pooled columns also go, input-dropped (index
+    // b*I + d, as lstm_in_fuse does), into the step's LSTM input row
     __shared__ float sa[MAX_L];
     __shared__ float red[8];
     __shared__ float part[16][128 + 4];
@@ -714,15 +684,26 @@ __global__ void attn_pool_fused_kernel(const bf16* __restrict__ ctx,
         float ssum = 0.f;
 #pragma unroll
         for (int g = 0; g < 16; ++g) ssum += part[g][tid];
-        pooled[(int64_t)b * D + d0 + tid] = f2bf(ssum);
+        bf16 pv = f2bf(ssum);
+        pooled[(int64_t)b * D + d0 + tid] = pv;
+        if (xh != nullptr) {
+            int d = d0 + tid;
+            xh[(int64_t)b * xh_stride + d] =
+                f2bf(bf2f(pv) * drop_scale((uint32_t)(*seed_p), salt,
+                                           (uint32_t)(b * I + d), p));
+        }
     }
 }
 
-std::vector<at::Tensor> attn_pool_fwd(at::Tensor ctx, at::Tensor logits) {
+static std::vector<at::Tensor> attn_pool_fwd_impl(
+        at::Tensor ctx, at::Tensor logits, bf16* xh_ptr,
+        const int64_t* seed_ptr, int xh_stride, int I, double p,
+        int64_t salt) {
     CHECK_GPU(ctx); CHECK_CONTIG(ctx); CHECK_BF16(ctx);
     CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_F32(logits);
     int B = ctx.size(0), L = ctx.size(1), D = ctx.size(2);
     TORCH_CHECK(L <= MAX_L, "attention locations exceed LDS stage");
+    TORCH_CHECK(logits.numel() == (int64_t)B * L);
     auto alpha = at::empty({B, L}, ctx.options().dtype(at::kFloat));
     auto pooled = at::empty({B, D}, ctx.options());
     hipStream_t s = at::cuda::getCurrentCUDAStream();
@@ -731,9 +712,31 @@ std::vector<at::Tensor> attn_pool_fwd(at::Tensor ctx, at::Tensor logits) {
                        (const bf16*)ctx.data_ptr(),
                        (const float*)logits.data_ptr(),
                        (float*)alpha.data_ptr(),
-                       (bf16*)pooled.data_ptr(), L, D);
+                       (bf16*)pooled.data_ptr(), L, D,
+                       xh_ptr, seed_ptr, xh_stride, I, (float)p,
+                       (int)salt);
     HIP_OK(hipGetLastError());
     return {alpha, pooled};
+}
+
+std::vector<at::Tensor> attn_pool_fwd(at::Tensor ctx, at::Tensor logits) {
+    return attn_pool_fwd_impl(ctx, logits, nullptr, nullptr, 0, 0, 0.0, 0);
+}
+
+// attn_pool_fwd that also writes dropout(pooled, p, salt) into columns
+// [0, D) of the step's LSTM input rows xh [B, I + H] (I = D + E)
+std::vector<at::Tensor> attn_pool_fwd_xh(at::Tensor ctx, at::Tensor logits,
+                                         at::Tensor seed, double p,
+                                         int64_t salt, at::Tensor xh,
+                                         int64_t I) {
+    CHECK_GPU(xh); CHECK_CONTIG(xh); CHECK_BF16(xh);
+    CHECK_GPU(seed);
+    TORCH_CHECK(xh.dim() == 2 && xh.size(0) == ctx.size(0)
+                && I >= ctx.size(2) && xh.size(1) >= I,
+                "xh must be [B, I + H] with I >= D");
+    return attn_pool_fwd_impl(ctx, logits, (bf16*)xh.data_ptr(),
+                              (const int64_t*)seed.data_ptr(),
+                              (int)xh.size(1), (int)I, p, salt);
 }
 
 // ======================================================================
