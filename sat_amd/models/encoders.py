@@ -50,11 +50,19 @@ class VGG16(tnn.Module):
                 layers.append(conv)
                 in_ch = out_ch
         self._layers = layers
-        # chained-pad fast path: conv1_1's direct kernel emits a 1-px
-        # zero-bordered output that conv1_2's glds igemm consumes
-        # without a pad pass (~70 us/step at 224^2 — models/nn.py)
-        self.conv1_1._emit_padded = True
-        self.conv1_2._accept_padded = True
+        # padded-output chain (models/nn.py PAD_CHAIN): every layer whose
+        # consumer is a 3x3 conv on an in-tree padded-input igemm kernel
+        # emits a 1-px zero-bordered output, which that conv reads
+        # without a pad1_nhwc pass.  A conv in front of a pool emits
+        # unpadded (the pool reads unpadded input) and conv5_3's output
+        # is the context grid.  Whether the consumer's route takes padded
+        # input depends on the batch, so the producer asks it per call
+        # (a bound method, not the module: no submodule is registered).
+        for prod, cons in zip(layers[:-1], layers[1:]):
+            if isinstance(cons, Conv2d) and cons.weight.shape[1] % 64 == 0:
+                prod._emit_padded = True
+                prod._pad_consumer_ok = cons._accepts_padded
+                cons._accept_padded = True
 
     def forward(self, images):
         """images: [B,3,224,224] -> contexts [B,196,512]."""

@@ -22,6 +22,43 @@ import torch.nn as tnn
 
 from .. import ops
 
+# Padded-output chain of the frozen VGG forward: every producer (conv or
+# pool) whose consumer is an in-tree padded-input 3x3 conv writes its
+# result straight into a 1-px zero-bordered buffer, so no pad1_nhwc pass
+# runs between them (profiles/pad_chain_perf_log.md; PAD_CHAIN_8P below
+# is the one exception).  False restores the pad1_nhwc routing everywhere
+# except conv1_1 -> conv1_2 (which chained before the switch existed); it
+# is there for A/B runs and tests.
+PAD_CHAIN = True
+
+# Whether the single-pass 8-phase kernel (conv3_x / conv4_x at batch 32)
+# also emits padded.  Measured, it should not: its padded epilogue costs
+# 24-27 us per layer, the pad1_nhwc pass it would remove 9-17 us
+# (profiles/pad_chain_perf_log.md), so those four pad passes stay.  The
+# pools, conv1_1, the glds kernel and the split-K combine kernel emit
+# padded at (almost) no cost.  True gives the pad-pass-free forward.
+PAD_CHAIN_8P = False
+
+# Route of the Cout%256 3x3 convs below the 8-phase kernel's chip-filling
+# size (conv5 at batch 32, M = 6272): 'intree' = split-K 8-phase kernel,
+# 'miopen' = the library's split-K igemm.  Decided end to end, all helper
+# kernels of both routes counted (profiles/pad_chain_perf_log.md).
+CONV5_ROUTE = 'intree'
+_8P_FULL_M = 12544      # 8-phase single pass fills the chip from here
+_8P_SPLIT_M = 6272      # smallest M measured on the split-K route
+
+
+def _8p_single_pass(Cout, Cin, M):
+    """conv_igemm_8p_fwd's own choice (conv8p.hip): True when it runs one
+    pass with the bf16 epilogue, False when it splits K and the combine
+    kernel writes the output."""
+    blocks = -(-Cout // 256) * -(-M // 256)
+    return min(8, 224 // blocks, 9 * (Cin // 64) // 2) <= 1
+
+
+def _unpad(x):
+    return x[:, :, 1:-1, 1:-1].contiguous(memory_format=torch.channels_last)
+
 
 class NN(object):
     """Policy object handed to every layer factory."""
@@ -193,20 +230,69 @@ class Conv2d(tnn.Module):
         else:
             self.register_parameter('bias', None)
 
+    def _igemm_route(self, M, padded_in=False):
+        """Frozen-GPU implicit-GEMM kernel for this 3x3/s1 layer at M
+        output pixels: '8p', 'glds', 'g64' (all three read a 1-px padded
+        input), 'ig64' (unpadded input) or None (library conv).
+
+        Per-shape winners (profiles/r01_conv_shapes.txt, r02 8-phase
+        kernel, profiles/pad_chain_perf_log.md for conv5):
+          * Cout%256==0 with enough output pixels to fill the chip at a
+            256^2 tile: the 8-phase deep-pipelined igemm (conv8p.hip) —
+            the Cin>=256 layers MIOpen used to keep; below that, down to
+            conv5 at batch 32, its split-K form when CONV5_ROUTE says so;
+          * Cin<=128 & Cout>=128: the XOR-swizzled glds variant
+            (120 vs 169 us on conv2_1);
+          * Cout<128 (conv1_2): glds64, 525 TF vs the register igemm's
+            350 (profiles/r02_conv_shapes.txt);
+          * Cin=64 without `use_glds_conv`: register-staged MFMA conv.
+        `use_glds_conv` gates all LDS-DMA-staged variants."""
+        Cout, Cin = self.weight.shape[0], self.weight.shape[1]
+        if (self.kernel_size != 3 or self.stride != 1
+                or Cout % 8 != 0 or Cin % 8 != 0):
+            return None
+        if self._glds_conv and Cin % 64 == 0:
+            min_m = _8P_SPLIT_M if CONV5_ROUTE == 'intree' else _8P_FULL_M
+            if Cout % 256 == 0 and M >= min_m:
+                return '8p'
+            if Cout >= 128 and Cin <= 128:
+                return 'glds'
+            if Cout < 128:
+                return 'g64'
+        if Cin == 64 and not padded_in:
+            return 'ig64'
+        return None
+
+    def _accepts_padded(self, M):
+        """Will forward() consume a 1-px padded input directly (frozen
+        GPU bf16 forward assumed, as in the producer that asks)?"""
+        return (getattr(self, '_accept_padded', False)
+                and self._igemm_route(M, True) in ('8p', 'glds', 'g64'))
+
+    def _emits_padded(self, M):
+        """Emit a padded output for the consumer wired by the encoder?
+        conv1_1 -> conv1_2 chained before PAD_CHAIN existed and stays on
+        with the switch off."""
+        if not (getattr(self, '_emit_padded', False) and self._glds_conv):
+            return False
+        if not (PAD_CHAIN or self.weight.shape[1] == 3):
+            return False
+        ok = getattr(self, '_pad_consumer_ok', None)
+        return ok is None or ok(M)
+
     def forward(self, x):
         w = self.weight.to(x.dtype)
         b = self.bias.to(x.dtype) if self.bias is not None else None
         k, st = self.kernel_size, self.stride
-        # chained-pad handshake: a producing conv may hand over a 1-px
-        # zero-bordered output (tagged `_sat_pad`); a 3x3/s1 consumer
+        # chained-pad handshake: a producing conv or pool may hand over a
+        # 1-px zero-bordered output (tagged `_sat_pad`); a 3x3/s1 consumer
         # marked _accept_padded uses it directly, anyone else unpads
         pad_hw = getattr(x, '_sat_pad', None)
         if pad_hw is not None and not (
                 getattr(self, '_accept_padded', False)
                 and k == 3 and st == 1
                 and not torch.is_grad_enabled()):
-            x = x[:, :, 1:-1, 1:-1] \
-                .contiguous(memory_format=torch.channels_last)
+            x = _unpad(x)
             pad_hw = None
         # --train_cnn: hand-written forward/dgrad/wgrad autograd triple
         # (reference model.py:505-511 backward surface on in-tree kernels)
@@ -232,8 +318,8 @@ class Conv2d(tnn.Module):
             from ..ops import hip
             if hip.available():
                 from sat_amd import _C
-                emit = bool(getattr(self, '_emit_padded', False)
-                            and self._glds_conv)
+                emit = self._emits_padded(
+                    x.shape[0] * x.shape[2] * x.shape[3])
                 y = _C.conv3_fwd(
                     x, w.contiguous(),
                     b if b is not None
@@ -242,15 +328,8 @@ class Conv2d(tnn.Module):
                 if emit:
                     y._sat_pad = (x.shape[2], x.shape[3])
                 return y
-        # frozen GPU implicit-GEMM paths (per-shape winners,
-        # profiles/r01_conv_shapes.txt + r02 8-phase kernel):
-        #  * Cout%256==0 with enough output pixels to fill the chip at a
-        #    256^2 tile: the 8-phase deep-pipelined igemm (conv8p.hip) —
-        #    the Cin>=256 layers MIOpen used to keep;
-        #  * Cin=64: register-staged MFMA conv (337 vs 407 us on conv1_2)
-        #  * Cin<=128 & Cout>=128: the XOR-swizzled glds variant
-        #    (120 vs 169 us on conv2_1); `use_glds_conv` gates both
-        #    LDS-staged variants.
+        # frozen GPU implicit-GEMM paths, routed per shape by
+        # _igemm_route()
         if (x.is_cuda and x.dtype == torch.bfloat16
                 and not torch.is_grad_enabled()
                 and k == 3 and st == 1
@@ -259,27 +338,12 @@ class Conv2d(tnn.Module):
             from ..ops import hip
             if hip.available():
                 from sat_amd import _C
-                Cout, Cin = w.shape[0], w.shape[1]
                 H = pad_hw[0] if pad_hw else x.shape[2]
                 W = pad_hw[1] if pad_hw else x.shape[3]
                 M = x.shape[0] * H * W
                 relu = self.activation == 'relu'
-                # 8p wins every Cout%256 shape with M>=12544; at
-                # conv5-batch-32 (M=6272) MIOpen gk still wins 77 vs
-                # 99us (profiles/r02_conv_shapes.txt) — evidence-routed
-                use_8p = (self._glds_conv and Cout % 256 == 0
-                          and Cin % 64 == 0 and M >= 12544)
-                use_glds = (self._glds_conv and not use_8p
-                            and Cout >= 128 and Cout % 8 == 0
-                            and Cin % 64 == 0 and Cin <= 128)
-                # Cout=64 class (conv1_2): glds64 525 TF vs the register
-                # igemm's 350 (profiles/r02_conv_shapes.txt)
-                use_g64 = (self._glds_conv and not use_8p
-                           and not use_glds and Cout < 128
-                           and Cin % 64 == 0)
-                use_ig64 = (not use_8p and not use_glds and not use_g64
-                            and Cin == 64 and pad_hw is None)
-                if use_8p or use_glds or use_g64 or use_ig64:
+                route = self._igemm_route(M, pad_hw is not None)
+                if route is not None:
                     if getattr(self, '_w_ohwi', None) is None or \
                             self._w_ohwi_ver != self.weight._version:
                         self._w_ohwi_ver = self.weight._version
@@ -287,18 +351,22 @@ class Conv2d(tnn.Module):
                             .reshape(w.shape[0], -1)
                     eb = (b if b is not None else
                           torch.empty(0, dtype=x.dtype, device=x.device))
-                    if use_ig64:
+                    if route == 'ig64':
                         return _C.conv_igemm_fwd(x, self._w_ohwi, eb,
                                                  relu)
                     xp = x if pad_hw is not None else _C.pad1_nhwc(x)
-                    if use_8p:
-                        return _C.conv_igemm_8p_fwd(
-                            xp, self._w_ohwi, eb, H, W, relu)
-                    if use_glds:
-                        return _C.conv_igemm_glds_fwd(
-                            xp, self._w_ohwi, eb, H, W, relu)
-                    return _C.conv_igemm_glds64_fwd(
-                        xp, self._w_ohwi, eb, H, W, relu)
+                    # the epilogue writes the next conv's zero border
+                    # itself when the encoder wired one that takes it
+                    emit = self._emits_padded(M) and (
+                        route != '8p' or PAD_CHAIN_8P
+                        or not _8p_single_pass(w.shape[0], w.shape[1], M))
+                    fwd = {'8p': _C.conv_igemm_8p_fwd,
+                           'glds': _C.conv_igemm_glds_fwd,
+                           'g64': _C.conv_igemm_glds64_fwd}[route]
+                    y = fwd(xp, self._w_ohwi, eb, H, W, relu, emit)
+                    if emit:
+                        y._sat_pad = (H, W)
+                    return y
         # 1x1/s1 conv IS a GEMM over the NHWC row view: route through
         # the in-tree tiled MFMA GEMM instead of MIOpen (ResNet50's
         # bottleneck convs; bias handled by the GEMM epilogue)
@@ -387,6 +455,8 @@ class MaxPool2d(tnn.Module):
         self.stride = stride
 
     def forward(self, x):
+        if getattr(x, '_sat_pad', None) is not None:
+            x = _unpad(x)           # pools read unpadded input only
         if (x.is_cuda and x.dtype == torch.bfloat16
                 and not torch.is_grad_enabled()
                 and self.kernel_size == 2 and self.stride == 2
@@ -395,7 +465,18 @@ class MaxPool2d(tnn.Module):
             from ..ops import hip
             if hip.available():
                 from sat_amd import _C
-                return _C.maxpool2x2_nhwc(x)
+                # padded-output chain (PAD_CHAIN): write the next conv's
+                # zero border here when the encoder wired one that takes it
+                Ho, Wo = (x.shape[2] + 1) // 2, (x.shape[3] + 1) // 2
+                ok = getattr(self, '_pad_consumer_ok', None)
+                emit = bool(PAD_CHAIN
+                            and getattr(self, '_emit_padded', False)
+                            and ok is not None
+                            and ok(x.shape[0] * Ho * Wo))
+                y = _C.maxpool2x2_nhwc(x, emit)
+                if emit:
+                    y._sat_pad = (Ho, Wo)
+                return y
         x = _pad_same(x, self.kernel_size, self.stride)
         return torch.nn.functional.max_pool2d(
             x, self.kernel_size, self.stride)

@@ -27,27 +27,32 @@ std::vector<at::Tensor> dense_dx_fuse(at::Tensor dgates, at::Tensor wl_t,
                                       double p, int64_t salt,
                                       int64_t D, int64_t E, int64_t H);
 at::Tensor conv3_fwd(at::Tensor input, at::Tensor weight, at::Tensor bias,
-                     bool relu, bool emit_pad);
+                     bool relu, bool emit_pad,
+                     c10::optional<at::Tensor> out);
 void bias_act_nhwc(at::Tensor y, at::Tensor bias, bool relu);
 void scale_bias_act_nhwc(at::Tensor y, at::Tensor scale, at::Tensor shift,
                          bool relu);
-at::Tensor maxpool2x2_nhwc(at::Tensor input);
+at::Tensor maxpool2x2_nhwc(at::Tensor input, bool emit_pad,
+                           c10::optional<at::Tensor> out);
 at::Tensor conv_igemm_fwd(at::Tensor input, at::Tensor w_ohwi,
                           at::Tensor bias, bool relu);
 at::Tensor pad1_nhwc(at::Tensor input);
 at::Tensor conv_igemm_8p_fwd(at::Tensor padded, at::Tensor w_ohwi,
                              at::Tensor bias, int64_t Hh, int64_t Ww,
-                             bool relu);
+                             bool relu, bool emit_pad,
+                             c10::optional<at::Tensor> out, int64_t split);
 at::Tensor conv_igemm_glds64_fwd(at::Tensor padded, at::Tensor w_ohwi,
                                  at::Tensor bias, int64_t Hh, int64_t Ww,
-                                 bool relu);
+                                 bool relu, bool emit_pad,
+                                 c10::optional<at::Tensor> out);
 at::Tensor dense_8p_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
                         int64_t act);
 at::Tensor conv3x3_wgrad(at::Tensor xpad, at::Tensor dy_rows,
                          int64_t Hh, int64_t Ww);
 at::Tensor conv_igemm_glds_fwd(at::Tensor padded, at::Tensor w_ohwi,
                                at::Tensor bias, int64_t Hh, int64_t Ww,
-                               bool relu);
+                               bool relu, bool emit_pad,
+                               c10::optional<at::Tensor> out);
 std::vector<at::Tensor> dense_lstm_fwd(at::Tensor xh, at::Tensor wl,
                                        at::Tensor bl, at::Tensor c_prev,
                                        double fb);
@@ -156,6 +161,14 @@ std::vector<at::Tensor> dexp_lstm_bwd_slabs(
     at::Tensor c_prev, at::Tensor dc, at::Tensor dgates_out, double p_fc,
     double p_lstm, int64_t s, int64_t D, int64_t E, double fb);
 
+// The frozen-VGG producers take `emit_pad` (write a 1-px zero-bordered
+// [B,C,H+2,W+2] output for the next 3x3 conv) and an optional caller-
+// supplied `out`; both default to the plain unpadded, freshly allocated
+// result.
+#define CONV_ARGS py::arg("padded"), py::arg("w_ohwi"), py::arg("bias"), \
+    py::arg("H"), py::arg("W"), py::arg("relu"),                         \
+    py::arg("emit_pad") = false, py::arg("out") = py::none()
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("dense_fwd", &dense_fwd, "MFMA GEMM + bias/act (bf16)");
     m.def("dense_fwd_drop", &dense_fwd_drop,
@@ -168,20 +181,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "dxh GEMM with the dx scatter fused into the epilogue");
     m.def("bias_act_nhwc", &bias_act_nhwc);
     m.def("scale_bias_act_nhwc", &scale_bias_act_nhwc);
-    m.def("maxpool2x2_nhwc", &maxpool2x2_nhwc);
+    m.def("maxpool2x2_nhwc", &maxpool2x2_nhwc, py::arg("input"),
+          py::arg("emit_pad") = false, py::arg("out") = py::none());
     m.def("conv_igemm_fwd", &conv_igemm_fwd);
     m.def("pad1_nhwc", &pad1_nhwc);
-    m.def("conv_igemm_glds_fwd", &conv_igemm_glds_fwd);
+    m.def("conv_igemm_glds_fwd", &conv_igemm_glds_fwd, CONV_ARGS);
     m.def("conv_igemm_8p_fwd", &conv_igemm_8p_fwd,
-          "8-phase deep-pipelined implicit-GEMM conv (Cout%256==0)");
-    m.def("conv_igemm_glds64_fwd", &conv_igemm_glds64_fwd);
+          "8-phase deep-pipelined implicit-GEMM conv (Cout%256==0); "
+          "split: -1 auto, 0 single pass, >= 2 that many K slices",
+          CONV_ARGS, py::arg("split") = -1);
+    m.def("conv_igemm_glds64_fwd", &conv_igemm_glds64_fwd, CONV_ARGS);
     m.def("dense_8p_fwd", &dense_8p_fwd,
           "8-phase deep-pipelined dense GEMM (big-M shapes)");
     m.def("conv3x3_wgrad", &conv3x3_wgrad,
           "3x3 conv weight grad: transpose-staged MFMA split-K reduce");
     m.def("dense_lstm_fwd", &dense_lstm_fwd);
     m.def("conv3_fwd", &conv3_fwd,
-          "direct NHWC conv for 3-channel 3x3/s1 (VGG conv1_1)");
+          "direct NHWC conv for 3-channel 3x3/s1 (VGG conv1_1)",
+          py::arg("input"), py::arg("weight"), py::arg("bias"),
+          py::arg("relu"), py::arg("emit_pad"),
+          py::arg("out") = py::none());
     m.def("lstm_pointwise_bwd_out", &lstm_pointwise_bwd_out);
     m.def("lstm_in_fuse", &lstm_in_fuse);
     m.def("expand_fuse", &expand_fuse);

@@ -131,6 +131,110 @@ __device__ __forceinline__ void lstm_cell_bwd(const float g[4], float cp,
     dcp = dct * a.gf;
 }
 
+// ---- "emit padded" output mode of the frozen-VGG producers ----
+// A producer may write its [B,H,W,C] result into the interior of a
+// [B,H+2,W+2,C] buffer and zero the 1-px border itself, so the next 3x3
+// conv's glds staging reads it without a pad1_nhwc pass.  The thread that
+// stores pixel (y,x) also zeroes the border pixels next to it, which
+// covers every border pixel exactly once and needs no state or launch.
+
+// Pixel row m of the [B,H,W] grid: (y,x) and the index of its interior
+// slot in the padded buffer, in pixels (below 2^31 whenever the padded
+// buffer has fewer than 2^31 pixels; the hosts check it).
+struct PadPix { int pix, y, x; };
+
+__device__ __forceinline__ PadPix pad_pix(int m, int H, int W) {
+    int b = m / (H * W);
+    int yx = m - b * (H * W);
+    PadPix p;
+    p.y = yx / W;
+    p.x = yx - p.y * W;
+    p.pix = (b * (H + 2) + p.y + 1) * (W + 2) + p.x + 1;
+    return p;
+}
+
+// step to pixel row m+1 without dividing again (a lane of an MFMA
+// epilogue owns runs of 4 consecutive rows); branch-free
+__device__ __forceinline__ void pad_pix_next(PadPix& p, int H, int W) {
+    const bool wx = (p.x + 1 == W);           // next image row
+    const bool wy = wx && (p.y + 1 == H);     // next image
+    p.pix += 1 + (wx ? 2 : 0) + (wy ? 2 * (W + 2) : 0);
+    p.y = wy ? 0 : (wx ? p.y + 1 : p.y);
+    p.x = wx ? 0 : p.x + 1;
+}
+
+// p = address of this thread's T-wide (bf16 or bf16x8) store at interior
+// pixel (y,x): zero the same channels of the adjacent border pixels.
+template <typename T>
+__device__ __forceinline__ void pad_border_zero(bf16* p, int y, int x,
+                                                int H, int W, int C) {
+    const bool l = (x == 0), r = (x == W - 1);
+    if (!(l || r || y == 0 || y == H - 1)) return;
+    const int64_t rs = (int64_t)(W + 2) * C;   // padded row stride
+    const T z = {};
+    if (l) *(T*)(p - C) = z;
+    if (r) *(T*)(p + C) = z;
+    if (y == 0) {
+        *(T*)(p - rs) = z;
+        if (l) *(T*)(p - rs - C) = z;
+        if (r) *(T*)(p - rs + C) = z;
+    }
+    if (y == H - 1) {
+        *(T*)(p + rs) = z;
+        if (l) *(T*)(p + rs - C) = z;
+        if (r) *(T*)(p + rs + C) = z;
+    }
+}
+
+// MFMA epilogues keep the border out of their unrolled store loops (128
+// inlined copies of the edge tests made the 8-phase epilogue ~60 KB of
+// straight-line code): after the stores, this compact loop walks a
+// lane's run of 4 rows from row0 and zeroes the border next to its edge
+// pixels in the lane's (up to 4) columns.
+__device__ __forceinline__ void pad_border_run(bf16* out, int row0, int M,
+                                               int H, int W, int C,
+                                               const int (&cols)[4]) {
+    if (row0 >= M) return;
+    PadPix p = pad_pix(row0, H, W);
+#pragma unroll 1
+    for (int r = 0; r < 4 && row0 + r < M; ++r) {
+        if (r) pad_pix_next(p, H, W);
+        if (p.x == 0 || p.x == W - 1 || p.y == 0 || p.y == H - 1) {
+            bf16* q = out + (int64_t)p.pix * C;
+#pragma unroll 1
+            for (int j = 0; j < 4; ++j)
+                if (cols[j] < C)
+                    pad_border_zero<bf16>(q + cols[j], p.y, p.x, H, W, C);
+        }
+    }
+}
+
+// Output of a producer: [B,C,H,W] channels-last, or [B,C,H+2,W+2] with
+// emit_pad.  A caller-supplied `out` is used in place of a fresh
+// allocation after its shape, dtype and layout are checked.
+static inline at::Tensor nhwc_out(const at::Tensor& like, int64_t B,
+                                  int64_t C, int64_t H, int64_t W,
+                                  bool emit_pad,
+                                  const c10::optional<at::Tensor>& out) {
+    const int64_t Ho = emit_pad ? H + 2 : H, Wo = emit_pad ? W + 2 : W;
+    TORCH_CHECK(B * Ho * Wo < (1LL << 31), "output has >= 2^31 pixels");
+    if (out.has_value() && out->defined()) {
+        CHECK_GPU(*out); CHECK_BF16(*out);
+        TORCH_CHECK(out->dim() == 4 && out->size(0) == B
+                    && out->size(1) == C && out->size(2) == Ho
+                    && out->size(3) == Wo,
+                    "out: expected [", B, ",", C, ",", Ho, ",", Wo, "]");
+        TORCH_CHECK(out->is_contiguous(at::MemoryFormat::ChannelsLast),
+                    "out must be channels_last");
+        TORCH_CHECK(out->device() == like.device(),
+                    "out must be on the input's device");
+        return *out;
+    }
+    return at::empty({B, C, Ho, Wo},
+                     like.options()
+                         .memory_format(at::MemoryFormat::ChannelsLast));
+}
+
 // split-K combine: element `off` summed over `splitk` fp32 slabs of n
 __device__ __forceinline__ float sum_slabs(const float* __restrict__ Yf,
                                            int64_t n, int64_t off,

@@ -62,11 +62,15 @@ void conv3_fwd_kernel(const bf16* __restrict__ in,   // [B,H,W,3]
     // emit_pad: write into the interior of a 1-px zero-bordered buffer
     // so the NEXT 3x3 conv consumes it without a pad pass (the thread
     // already knows (b,y,x) — the padded store is free here, while a
-    // separate pad1_nhwc of a 224^2 x64 tensor costs ~70 us)
+    // separate pad1_nhwc of a 224^2 x64 tensor costs ~70 us); edge
+    // pixels zero the border next to them (common.h)
     bf16* op = emit_pad
         ? out + ((((int64_t)b * (Hh + 2) + y + 1) * (Ww + 2) + x + 1)
                  * Cout)
         : out + (int64_t)pix * Cout;
+    if (emit_pad)
+        for (int c0 = 0; c0 < Cout; c0 += 8)
+            pad_border_zero<bf16x8>(op + c0, y, x, Hh, Ww, Cout);
     for (int c0 = 0; c0 < Cout; c0 += 8) {
         bf16x8 o;
 #pragma unroll
@@ -83,29 +87,9 @@ void conv3_fwd_kernel(const bf16* __restrict__ in,   // [B,H,W,3]
     }
 }
 
-// zero only the 1-px border of a padded NHWC buffer (the interior is
-// fully overwritten by the producing conv)
-__global__ void zero_border_kernel(bf16* __restrict__ out,
-                                   int B, int Hp, int Wp, int C) {
-    int64_t border = (int64_t)B * 2 * (Hp + Wp - 2);  // border pixels
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t n = border * (C / 8);
-    if (i >= n) return;
-    int c8 = (int)(i % (C / 8)) * 8;
-    int64_t pb = i / (C / 8);
-    int b = (int)(pb / (2 * (Hp + Wp - 2)));
-    int q = (int)(pb % (2 * (Hp + Wp - 2)));
-    int y, x;
-    if (q < Wp) { y = 0; x = q; }
-    else if (q < 2 * Wp) { y = Hp - 1; x = q - Wp; }
-    else if (q < 2 * Wp + (Hp - 2)) { y = q - 2 * Wp + 1; x = 0; }
-    else { y = q - 2 * Wp - (Hp - 2) + 1; x = Wp - 1; }
-    bf16x8 z = {};
-    *(bf16x8*)(out + (((int64_t)b * Hp + y) * Wp + x) * C + c8) = z;
-}
-
 at::Tensor conv3_fwd(at::Tensor input, at::Tensor weight, at::Tensor bias,
-                     bool relu, bool emit_pad) {
+                     bool relu, bool emit_pad,
+                     c10::optional<at::Tensor> out_opt) {
     // input NHWC-contiguous [B,3,H,W] tensor in channels_last
     CHECK_GPU(input); CHECK_BF16(input);
     CHECK_GPU(weight); CHECK_BF16(weight);
@@ -118,25 +102,12 @@ at::Tensor conv3_fwd(at::Tensor input, at::Tensor weight, at::Tensor bias,
     int Cout = weight.size(0);
     TORCH_CHECK(Cout % 8 == 0 && Cout <= MAX_COUT);
     auto wc = weight.contiguous();  // OIHW
-    auto out = emit_pad
-        ? at::empty({B, Cout, Hh + 2, Ww + 2},
-                    input.options()
-                        .memory_format(at::MemoryFormat::ChannelsLast))
-        : at::empty({B, Cout, Hh, Ww},
-                    input.options()
-                        .memory_format(at::MemoryFormat::ChannelsLast));
+    auto out = nhwc_out(input, B, Cout, Hh, Ww, emit_pad, out_opt);
     const bf16* bias_ptr = nullptr;
     if (bias.defined() && bias.numel() > 0)
         bias_ptr = (const bf16*)bias.contiguous().data_ptr();
     int BHW = B * Hh * Ww;
     hipStream_t s = at::cuda::getCurrentCUDAStream();
-    if (emit_pad) {
-        int64_t nb = (int64_t)B * 2 * (Hh + 2 + Ww + 2 - 2) * (Cout / 8);
-        hipLaunchKernelGGL(zero_border_kernel, dim3(cdiv(nb, 256)),
-                           dim3(256), 0, s,
-                           (bf16*)out.data_ptr(), B, Hh + 2, Ww + 2,
-                           Cout);
-    }
     hipLaunchKernelGGL(conv3_fwd_kernel, dim3(cdiv(BHW, 256)), dim3(256),
                        0, s,
                        (const bf16*)input.data_ptr(),
@@ -189,7 +160,9 @@ void bias_act_nhwc(at::Tensor y, at::Tensor bias, bool relu) {
 __global__ void maxpool2x2_nhwc_kernel(const bf16* __restrict__ in,
                                        bf16* __restrict__ out,
                                        int B, int H, int W, int C,
-                                       int Ho, int Wo) {
+                                       int Ho, int Wo, int emit_pad) {
+    // emit_pad: out is [B,Ho+2,Wo+2,C] with a zero border (common.h);
+    // the input is always unpadded
     int64_t i8 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     int64_t n = (int64_t)B * Ho * Wo * C;
     if (i8 >= n) return;
@@ -221,25 +194,33 @@ __global__ void maxpool2x2_nhwc_kernel(const bf16* __restrict__ in,
                 if (bf2f(v[e]) > bf2f(m[e])) m[e] = v[e];
         }
     }
-    *(bf16x8*)(out + i8) = m;
+    if (emit_pad) {
+        bf16* op = out
+            + (((int64_t)b * (Ho + 2) + yo + 1) * (Wo + 2) + xo + 1) * C
+            + c;
+        *(bf16x8*)op = m;
+        pad_border_zero<bf16x8>(op, yo, xo, Ho, Wo, C);
+    } else {
+        *(bf16x8*)(out + i8) = m;
+    }
 }
 
-at::Tensor maxpool2x2_nhwc(at::Tensor input) {
+at::Tensor maxpool2x2_nhwc(at::Tensor input, bool emit_pad,
+                           c10::optional<at::Tensor> out_opt) {
     CHECK_GPU(input); CHECK_BF16(input);
     TORCH_CHECK(input.is_contiguous(at::MemoryFormat::ChannelsLast));
     int B = input.size(0), C = input.size(1), H = input.size(2),
         W = input.size(3);
     TORCH_CHECK(C % 8 == 0);
     int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    auto out = at::empty({B, C, Ho, Wo},
-                         input.options()
-                             .memory_format(at::MemoryFormat::ChannelsLast));
+    auto out = nhwc_out(input, B, C, Ho, Wo, emit_pad, out_opt);
     int64_t n = (int64_t)B * Ho * Wo * C;
     hipStream_t s = at::cuda::getCurrentCUDAStream();
     hipLaunchKernelGGL(maxpool2x2_nhwc_kernel, dim3(cdiv(n / 8, 256)),
                        dim3(256), 0, s,
                        (const bf16*)input.data_ptr(),
-                       (bf16*)out.data_ptr(), B, H, W, C, Ho, Wo);
+                       (bf16*)out.data_ptr(), B, H, W, C, Ho, Wo,
+                       emit_pad ? 1 : 0);
     HIP_OK(hipGetLastError());
     return out;
 }
@@ -517,7 +498,7 @@ void conv_igemm_glds_kernel(const bf16* __restrict__ inp,  // padded NHWC
                             const bf16* __restrict__ bias,
                             bf16* __restrict__ out,
                             int M, int Hh, int Ww, int Cin, int Cout,
-                            int relu) {
+                            int relu, int emit_pad) {
     // output pixel grid is the UNPADDED HxW; input rows live in the
     // padded (H+2)x(W+2) image so every (dy,dx) shift is in bounds.
     constexpr int BM = 128, BN = 128, BKc = 64;
@@ -623,28 +604,51 @@ void conv_igemm_glds_kernel(const bf16* __restrict__ inp,  // padded NHWC
         __syncthreads();
     }
 
+    // epilogue, one output row at a time: with emit_pad the row goes to
+    // the interior of a zero-bordered [B,H+2,W+2,Cout] buffer, and a
+    // compact loop after the stores zeroes the border next to the edge
+    // pixels (common.h)
+    const int col0 = bn + wc * 64 + (lane & 15);
+    float bv[4];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
-        int col = bn + wc * 64 + ni * 16 + (lane & 15);
-        float bv = (bias != nullptr && col < Cout) ? bf2f(bias[col]) : 0.f;
+        int col = col0 + ni * 16;
+        bv[ni] = (bias != nullptr && col < Cout) ? bf2f(bias[col]) : 0.f;
+    }
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
+    for (int mi = 0; mi < 4; ++mi) {
+        const int row0 = bm + wr * 64 + mi * 16 + (lane >> 4) * 4;
+        PadPix pr = {0, 0, 0};
+        if (emit_pad) pr = pad_pix(min(row0, M - 1), Hh, Ww);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = bm + wr * 64 + mi * 16 + (lane >> 4) * 4 + r;
+        for (int r = 0; r < 4; ++r) {
+            int row = row0 + r;
+            if (emit_pad && r > 0) pad_pix_next(pr, Hh, Ww);
+            bf16* orow = out + (int64_t)(emit_pad ? pr.pix : row) * Cout;
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                int col = col0 + ni * 16;
                 if (row < M && col < Cout) {
-                    float vv = acc[mi][ni][r] + bv;
+                    float vv = acc[mi][ni][r] + bv[ni];
                     if (relu) vv = fmaxf(vv, 0.f);
-                    out[(int64_t)row * Cout + col] = f2bf(vv);
+                    orow[col] = f2bf(vv);
                 }
             }
         }
+    }
+    if (emit_pad) {                           // border: compact loop
+        const int cols[4] = {col0, col0 + 16, col0 + 32, col0 + 48};
+#pragma unroll 1
+        for (int mi = 0; mi < 4; ++mi)
+            pad_border_run(out, bm + wr * 64 + mi * 16 + (lane >> 4) * 4,
+                           M, Hh, Ww, Cout, cols);
     }
 }
 
 at::Tensor conv_igemm_glds_fwd(at::Tensor padded, at::Tensor w_ohwi,
                                at::Tensor bias, int64_t Hh, int64_t Ww,
-                               bool relu) {
+                               bool relu, bool emit_pad,
+                               c10::optional<at::Tensor> out_opt) {
     CHECK_GPU(padded); CHECK_BF16(padded);
     CHECK_GPU(w_ohwi); CHECK_CONTIG(w_ohwi); CHECK_BF16(w_ohwi);
     TORCH_CHECK(padded.is_contiguous(at::MemoryFormat::ChannelsLast));
@@ -652,9 +656,7 @@ at::Tensor conv_igemm_glds_fwd(at::Tensor padded, at::Tensor w_ohwi,
     TORCH_CHECK(padded.size(2) == Hh + 2 && padded.size(3) == Ww + 2);
     int Cout = w_ohwi.size(0);
     TORCH_CHECK(Cin % 64 == 0 && Cout % 8 == 0);
-    auto out = at::empty({B, Cout, Hh, Ww},
-                         padded.options()
-                             .memory_format(at::MemoryFormat::ChannelsLast));
+    auto out = nhwc_out(padded, B, Cout, Hh, Ww, emit_pad, out_opt);
     const bf16* bias_ptr = nullptr;
     if (bias.defined() && bias.numel() > 0)
         bias_ptr = (const bf16*)bias.contiguous().data_ptr();
@@ -665,7 +667,8 @@ at::Tensor conv_igemm_glds_fwd(at::Tensor padded, at::Tensor w_ohwi,
                        (const bf16*)padded.data_ptr(),
                        (const bf16*)w_ohwi.data_ptr(), bias_ptr,
                        (bf16*)out.data_ptr(), (int)M, (int)Hh, (int)Ww,
-                       (int)Cin, (int)Cout, relu ? 1 : 0);
+                       (int)Cin, (int)Cout, relu ? 1 : 0,
+                       emit_pad ? 1 : 0);
     HIP_OK(hipGetLastError());
     return out;
 }
@@ -676,13 +679,15 @@ at::Tensor conv_igemm_glds_fwd(at::Tensor padded, at::Tensor w_ohwi,
 // <4,1,2,4> kernel measured 350 TF on conv1_2 while the glds-staged
 // 128x128 class reaches 536-658 TF; Cout=64 layers could not use it.
 
-__global__ __launch_bounds__(256)
+// (256, 5): keep the 5 waves/SIMD the kernel had before the padded-emit
+// epilogue, whose address registers would otherwise cost a wave
+__global__ __launch_bounds__(256, 5)
 void conv_igemm_glds64_kernel(const bf16* __restrict__ inp, // padded
                               const bf16* __restrict__ w,   // [Cout,9Ci]
                               const bf16* __restrict__ bias,
                               bf16* __restrict__ out,
                               int M, int Hh, int Ww, int Cin, int Cout,
-                              int relu) {
+                              int relu, int emit_pad) {
     constexpr int BM = 128, BKc = 64;
     __shared__ bf16 lds[(BM + 64) * BKc];   // A[128][64] + B[64][64]
     bf16* As = lds;
@@ -787,28 +792,48 @@ void conv_igemm_glds64_kernel(const bf16* __restrict__ inp, // padded
         __syncthreads();
     }
 
+    // epilogue by output row, emit_pad as in conv_igemm_glds_kernel
+    const int col0 = bn + (lane & 15);
+    float bv[4];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
-        int col = bn + ni * 16 + (lane & 15);
-        float bv = (bias != nullptr && col < Cout) ? bf2f(bias[col]) : 0.f;
+        int col = col0 + ni * 16;
+        bv[ni] = (bias != nullptr && col < Cout) ? bf2f(bias[col]) : 0.f;
+    }
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
+    for (int mi = 0; mi < 2; ++mi) {
+        const int row0 = bm + wave * 32 + mi * 16 + (lane >> 4) * 4;
+        PadPix pr = {0, 0, 0};
+        if (emit_pad) pr = pad_pix(min(row0, M - 1), Hh, Ww);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                int row = bm + wave * 32 + mi * 16 + (lane >> 4) * 4 + r;
+        for (int r = 0; r < 4; ++r) {
+            int row = row0 + r;
+            if (emit_pad && r > 0) pad_pix_next(pr, Hh, Ww);
+            bf16* orow = out + (int64_t)(emit_pad ? pr.pix : row) * Cout;
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                int col = col0 + ni * 16;
                 if (row < M && col < Cout) {
-                    float vv = acc[mi][ni][r] + bv;
+                    float vv = acc[mi][ni][r] + bv[ni];
                     if (relu) vv = fmaxf(vv, 0.f);
-                    out[(int64_t)row * Cout + col] = f2bf(vv);
+                    orow[col] = f2bf(vv);
                 }
             }
         }
+    }
+    if (emit_pad) {                           // border: compact loop
+        const int cols[4] = {col0, col0 + 16, col0 + 32, col0 + 48};
+#pragma unroll 1
+        for (int mi = 0; mi < 2; ++mi)
+            pad_border_run(out, bm + wave * 32 + mi * 16 + (lane >> 4) * 4,
+                           M, Hh, Ww, Cout, cols);
     }
 }
 
 at::Tensor conv_igemm_glds64_fwd(at::Tensor padded, at::Tensor w_ohwi,
                                  at::Tensor bias, int64_t Hh, int64_t Ww,
-                                 bool relu) {
+                                 bool relu, bool emit_pad,
+                                 c10::optional<at::Tensor> out_opt) {
     CHECK_GPU(padded); CHECK_BF16(padded);
     CHECK_GPU(w_ohwi); CHECK_CONTIG(w_ohwi); CHECK_BF16(w_ohwi);
     TORCH_CHECK(padded.is_contiguous(at::MemoryFormat::ChannelsLast));
@@ -816,9 +841,7 @@ at::Tensor conv_igemm_glds64_fwd(at::Tensor padded, at::Tensor w_ohwi,
     TORCH_CHECK(padded.size(2) == Hh + 2 && padded.size(3) == Ww + 2);
     int Cout = w_ohwi.size(0);
     TORCH_CHECK(Cin % 64 == 0 && Cout % 8 == 0);
-    auto out = at::empty({B, Cout, Hh, Ww},
-                         padded.options()
-                             .memory_format(at::MemoryFormat::ChannelsLast));
+    auto out = nhwc_out(padded, B, Cout, Hh, Ww, emit_pad, out_opt);
     const bf16* bias_ptr = nullptr;
     if (bias.defined() && bias.numel() > 0)
         bias_ptr = (const bf16*)bias.contiguous().data_ptr();
@@ -829,7 +852,8 @@ at::Tensor conv_igemm_glds64_fwd(at::Tensor padded, at::Tensor w_ohwi,
                        (const bf16*)padded.data_ptr(),
                        (const bf16*)w_ohwi.data_ptr(), bias_ptr,
                        (bf16*)out.data_ptr(), (int)M, (int)Hh, (int)Ww,
-                       (int)Cin, (int)Cout, relu ? 1 : 0);
+                       (int)Cin, (int)Cout, relu ? 1 : 0,
+                       emit_pad ? 1 : 0);
     HIP_OK(hipGetLastError());
     return out;
 }

@@ -30,8 +30,9 @@
 // rows aH*128 + wr*64 + mi*16, cols bH*128 + wc*32 + ni*16.
 //
 // Routing (sat_amd/models/nn.py): frozen-CNN forward, Cin % 64 == 0,
-// Cout % 256 == 0, padded input from pad1_nhwc.  Row/weight bases are
-// int64 (batch-512-per-GPU safe — r01 audit note).
+// Cout % 256 == 0, padded input from the producing layer's emit_pad
+// epilogue (or pad1_nhwc).  Row/weight bases are int64 (batch-512-per-GPU
+// safe — r01 audit note).
 
 #include "common.h"
 
@@ -65,7 +66,7 @@ void conv_igemm_8p_kernel(const bf16* __restrict__ inp,  // padded NHWC
                           bf16* __restrict__ out,
                           float* __restrict__ outf,
                           int M, int Hh, int Ww, int Cin, int Cout,
-                          int relu, int kt_per) {
+                          int relu, int kt_per, int emit_pad) {
     __shared__ bf16 lds[8 * SLOT];            // ONE shared object (guide
                                               // §5 trap 4a) = 128 KiB
 
@@ -259,6 +260,28 @@ void conv_igemm_8p_kernel(const bf16* __restrict__ inp,  // padded NHWC
 #undef B_DELTA
 
     // ---- epilogue: bias + ReLU + guarded store (or split-K atomics) ----
+    // SPLIT=0 with emit_pad: row m goes to its slot prow in the interior
+    // of a zero-bordered [B,H+2,W+2,Cout] buffer (common.h); the store
+    // loop is the unpadded one with prow in place of the row, and the
+    // border is zeroed by a compact loop after it.  The split-K scratch
+    // stays unpadded; f32_bias_act_nhwc_kernel pads instead.
+    int prow[8][4];                           // [aH*4+mi][r]
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int row0 = bm + (i >> 2) * 128 + wr * 64 + (i & 3) * 16
+            + (lane >> 4) * 4;
+        if (!SPLIT && emit_pad) {
+            PadPix p = pad_pix(min(row0, M - 1), Hh, Ww);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (r) pad_pix_next(p, Hh, Ww);
+                prow[i][r] = p.pix;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) prow[i][r] = row0 + r;
+        }
+    }
 #pragma unroll
     for (int bH = 0; bH < 2; ++bH) {
 #pragma unroll
@@ -283,8 +306,8 @@ void conv_igemm_8p_kernel(const bf16* __restrict__ inp,  // padded NHWC
                                 float v = acc[aH * 4 + mi]
                                     [bH * 2 + ni][r] + bv;
                                 if (relu) v = fmaxf(v, 0.f);
-                                out[(int64_t)row * Cout + col]
-                                    = f2bf(v);
+                                out[(int64_t)prow[aH * 4 + mi][r] * Cout
+                                    + col] = f2bf(v);
                             }
                         }
                     }
@@ -292,28 +315,53 @@ void conv_igemm_8p_kernel(const bf16* __restrict__ inp,  // padded NHWC
             }
         }
     }
+    if (!SPLIT && emit_pad) {
+        const int c0 = bn + wc * 32 + (lane & 15);
+        const int cols[4] = {c0, c0 + 16, c0 + 128, c0 + 144};
+#pragma unroll 1
+        for (int i = 0; i < 8; ++i)
+            pad_border_run(out, bm + (i >> 2) * 128 + wr * 64
+                           + (i & 3) * 16 + (lane >> 4) * 4,
+                           M, Hh, Ww, Cout, cols);
+    }
 }
 
 // fp32 split-K scratch -> bias + act -> bf16 NHWC
 __global__ void f32_bias_act_nhwc_kernel(const float* __restrict__ yf,
                                          const bf16* __restrict__ bias,
                                          bf16* __restrict__ out,
-                                         int64_t n, int C, int relu) {
+                                         int64_t n, int C, int relu,
+                                         int Hh, int Ww, int emit_pad) {
+    // yf is always the unpadded [M, C] scratch; emit_pad: out is the
+    // zero-bordered [B,H+2,W+2,C] buffer (common.h)
     int64_t i8 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
     if (i8 >= n) return;
     int c0 = (int)(i8 % C);
+    bf16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         float t = yf[i8 + e];
         if (bias != nullptr) t += bf2f(bias[c0 + e]);
         if (relu) t = fmaxf(t, 0.f);
-        out[i8 + e] = f2bf(t);
+        o[e] = f2bf(t);
+    }
+    if (emit_pad) {
+        PadPix pr = pad_pix((int)(i8 / C), Hh, Ww);
+        bf16* op = out + (int64_t)pr.pix * C + c0;
+        *(bf16x8*)op = o;
+        pad_border_zero<bf16x8>(op, pr.y, pr.x, Hh, Ww, C);
+    } else {
+        *(bf16x8*)(out + i8) = o;
     }
 }
 
+// split: -1 picks the split-K factor from the shape (the default), 0 or 1
+// forces the single-pass SPLIT=0 kernel, >= 2 forces that many K slices
 at::Tensor conv_igemm_8p_fwd(at::Tensor padded, at::Tensor w_ohwi,
                              at::Tensor bias, int64_t Hh, int64_t Ww,
-                             bool relu) {
+                             bool relu, bool emit_pad,
+                             c10::optional<at::Tensor> out_opt,
+                             int64_t split) {
     CHECK_GPU(padded); CHECK_BF16(padded);
     CHECK_GPU(w_ohwi); CHECK_CONTIG(w_ohwi); CHECK_BF16(w_ohwi);
     TORCH_CHECK(padded.is_contiguous(at::MemoryFormat::ChannelsLast));
@@ -323,9 +371,7 @@ at::Tensor conv_igemm_8p_fwd(at::Tensor padded, at::Tensor w_ohwi,
     TORCH_CHECK(Cin % 64 == 0 && Cin >= 64, "conv_igemm_8p: Cin % 64");
     TORCH_CHECK(Cout % 256 == 0, "conv_igemm_8p: Cout % 256");
     TORCH_CHECK(w_ohwi.numel() == (int64_t)Cout * 9 * Cin);
-    auto out = at::empty({B, Cout, Hh, Ww},
-                         padded.options()
-                             .memory_format(at::MemoryFormat::ChannelsLast));
+    auto out = nhwc_out(padded, B, Cout, Hh, Ww, emit_pad, out_opt);
     const bf16* bias_ptr = nullptr;
     if (bias.defined() && bias.numel() > 0)
         bias_ptr = (const bf16*)bias.contiguous().data_ptr();
@@ -335,6 +381,8 @@ at::Tensor conv_igemm_8p_fwd(at::Tensor padded, at::Tensor w_ohwi,
     int blocks = cdiv(Cout, 256) * cdiv(M, 256);
     int KT = 9 * (Cin / 64);
     int splitz = std::max(1, std::min({8, 224 / blocks, KT / 2}));
+    if (split >= 0)
+        splitz = std::max(1, std::min((int)split, KT));
     hipStream_t s = at::cuda::getCurrentCUDAStream();
     if (splitz > 1) {
         auto scratch = at::zeros({M, Cout},
@@ -348,13 +396,14 @@ at::Tensor conv_igemm_8p_fwd(at::Tensor padded, at::Tensor w_ohwi,
                            (const bf16*)w_ohwi.data_ptr(), bias_ptr,
                            nullptr, (float*)scratch.data_ptr(),
                            M, (int)Hh, (int)Ww,
-                           (int)Cin, (int)Cout, relu ? 1 : 0, kt_per);
+                           (int)Cin, (int)Cout, relu ? 1 : 0, kt_per, 0);
         int64_t n = (int64_t)M * Cout;
         hipLaunchKernelGGL(f32_bias_act_nhwc_kernel,
                            dim3(cdiv(n / 8, 256)), dim3(256), 0, s,
                            (const float*)scratch.data_ptr(), bias_ptr,
                            (bf16*)out.data_ptr(), n, (int)Cout,
-                           relu ? 1 : 0);
+                           relu ? 1 : 0, (int)Hh, (int)Ww,
+                           emit_pad ? 1 : 0);
     } else {
         dim3 grid(cdiv(Cout, 256), cdiv(M, 256));
         hipLaunchKernelGGL((conv_igemm_8p_kernel<0>), grid, dim3(512),
@@ -363,7 +412,8 @@ at::Tensor conv_igemm_8p_fwd(at::Tensor padded, at::Tensor w_ohwi,
                            (const bf16*)w_ohwi.data_ptr(), bias_ptr,
                            (bf16*)out.data_ptr(), nullptr,
                            M, (int)Hh, (int)Ww,
-                           (int)Cin, (int)Cout, relu ? 1 : 0, KT);
+                           (int)Cin, (int)Cout, relu ? 1 : 0, KT,
+                           emit_pad ? 1 : 0);
     }
     HIP_OK(hipGetLastError());
     return out;
