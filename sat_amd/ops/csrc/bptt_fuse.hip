@@ -428,8 +428,10 @@ at::Tensor hash_dropout_slabs(at::Tensor x, at::Tensor seed, double p,
 // d_out_carry arrives either as bf16, or (carry_slabs != null) as the
 // fp32 split-K slabs of the producing step's dodrop GEMM, finished here
 // exactly as skinny_epilogue_drop_kernel would: sum, ODROP mask of
-// carry_salt, one bf16 rounding ----
+// carry_salt, one bf16 rounding.  S < 0: bf16 carry; S > 0: that many
+// slabs, known at compile time; S == 0: carry_splitk slabs ----
 
+template <int S>
 __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
                                      const bf16* __restrict__ d_out_carry,
                                      const bf16* __restrict__ d_sth_carry,
@@ -448,41 +450,57 @@ __global__ void dexp_lstm_bwd_kernel(const bf16* __restrict__ dexpd,
                                      int carry_splitk, int carry_salt) {
     const uint32_t seed = (uint32_t)(*seed_p);
     const int W = H + D + E;
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)B * W) return;
-    int b = idx / W, j = idx % W;
+    // B * W and 4 * B * H < 2^31 (the host checks it)
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * W) return;
+    int b = idx / W, j = idx - b * W;
     float dexp = bf2f(dexpd[idx])
         * drop_scale(seed, s + 6, (uint32_t)(b * W + j), p_fc);
     if (j < H) {
-        uint32_t hidx = (uint32_t)(b * H + j);
+        const int hi = b * H + j;
+        uint32_t hidx = (uint32_t)hi;
+        // every load of the thread goes out before the first use: the
+        // carry (slabs or bf16), the state carry, the four gates, c and
+        // dc.  dc's address is valid with or without a dc (the value is
+        // dropped without one), so no load sits behind a branch.
+        float cs[S > 0 ? S : 1];
+        bf16 cb = {};
+        if constexpr (S > 0) load_slabs<S>(carry_slabs, B * H, hi, cs);
+        if constexpr (S < 0) cb = d_out_carry[hi];
+        bf16 sc = d_sth_carry[hi];
+        const bf16* gp = gates + b * 4 * H + j;
+        bf16 gb[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) gb[q] = gp[q * H];
+        bf16 cv = c[hi];
+        bf16 dcb = (dc != nullptr ? dc : c)[hi];
+
         float doc;
-        if (carry_slabs != nullptr) {
-            float v = sum_slabs(carry_slabs, (int64_t)B * H,
-                                (int64_t)b * H + j, carry_splitk);
+        if constexpr (S >= 0) {
+            float v;
+            if constexpr (S > 0) v = add_slabs<S>(cs);
+            else v = sum_slabs<0>(carry_slabs, B * H, hi, carry_splitk);
             v *= drop_scale(seed, carry_salt, hidx, p_fc);
             doc = bf2f(f2bf(v));
         } else {
-            doc = bf2f(d_out_carry[(int64_t)b * H + j]);
+            doc = bf2f(cb);
         }
         float dout = dexp + doc;
         float dhv = dout * drop_scale(seed, s + 4, hidx, p_lstm)
-            + bf2f(d_sth_carry[(int64_t)b * H + j])
-            * drop_scale(seed, s + 5, hidx, p_lstm);
-        const bf16* gp = gates + (int64_t)b * 4 * H + j;
+            + bf2f(sc) * drop_scale(seed, s + 5, hidx, p_lstm);
         float g[4], dg[4], dcp;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = bf2f(gp[q * H]);
-        float dcv = (dc != nullptr) ? bf2f(dc[(int64_t)b * H + j]) : 0.f;
-        lstm_cell_bwd(g, bf2f(c[(int64_t)b * H + j]), dhv, dcv, fb, dg,
-                      dcp);
-        bf16* dgp = dgates + (int64_t)b * 4 * H + j;
+        for (int q = 0; q < 4; ++q) g[q] = bf2f(gb[q]);
+        float dcv = (dc != nullptr) ? bf2f(dcb) : 0.f;
+        lstm_cell_bwd(g, bf2f(cv), dhv, dcv, fb, dg, dcp);
+        bf16* dgp = dgates + b * 4 * H + j;
 #pragma unroll
         for (int q = 0; q < 4; ++q) dgp[q * H] = f2bf(dg[q]);
-        dc_prev[(int64_t)b * H + j] = f2bf(dcp);
+        dc_prev[hi] = f2bf(dcp);
     } else if (j < H + D) {
-        dpool_dec[(int64_t)b * D + (j - H)] = f2bf(dexp);
+        dpool_dec[b * D + (j - H)] = f2bf(dexp);
     } else {
-        demb_dec[(int64_t)b * E + (j - H - D)] = f2bf(dexp);
+        demb_dec[b * E + (j - H - D)] = f2bf(dexp);
     }
 }
 
@@ -503,21 +521,30 @@ static std::vector<at::Tensor> dexp_lstm_bwd_impl(
     if (dc.defined() && dc.numel() > 0)
         dc_ptr = (const bf16*)dc.data_ptr();
     int64_t n = (int64_t)B * (H + D + E);
+    TORCH_CHECK(n < (1LL << 31) && (int64_t)B * 4 * H < (1LL << 31),
+                "expand row or gates have >= 2^31 elements");
     hipStream_t st = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(dexp_lstm_bwd_kernel, dim3(cdiv(n, 256)),
-                       dim3(256), 0, st,
-                       (const bf16*)dexpd.data_ptr(), carry_ptr,
-                       (const bf16*)d_sth_carry.data_ptr(),
-                       (const int64_t*)seed.data_ptr(),
-                       (const bf16*)gates.data_ptr(),
-                       (const bf16*)c_prev.data_ptr(), dc_ptr,
-                       (bf16*)dgates_out.data_ptr(),
-                       (bf16*)dc_prev.data_ptr(),
-                       (bf16*)dpool_dec.data_ptr(),
-                       (bf16*)demb_dec.data_ptr(),
-                       B, H, (int)D, (int)E,
-                       (float)p_fc, (float)p_lstm, (int)s, (float)fb,
-                       slab_ptr, carry_splitk, (int)carry_salt);
+#define LAUNCH_DEXP(S) \
+    hipLaunchKernelGGL(dexp_lstm_bwd_kernel<S>, dim3(cdiv(n, 256)), \
+                       dim3(256), 0, st, \
+                       (const bf16*)dexpd.data_ptr(), carry_ptr, \
+                       (const bf16*)d_sth_carry.data_ptr(), \
+                       (const int64_t*)seed.data_ptr(), \
+                       (const bf16*)gates.data_ptr(), \
+                       (const bf16*)c_prev.data_ptr(), dc_ptr, \
+                       (bf16*)dgates_out.data_ptr(), \
+                       (bf16*)dc_prev.data_ptr(), \
+                       (bf16*)dpool_dec.data_ptr(), \
+                       (bf16*)demb_dec.data_ptr(), \
+                       B, H, (int)D, (int)E, \
+                       (float)p_fc, (float)p_lstm, (int)s, (float)fb, \
+                       slab_ptr, carry_splitk, (int)carry_salt)
+    if (slab_ptr == nullptr) {
+        LAUNCH_DEXP(-1);
+    } else {
+        SLAB_DISPATCH(carry_splitk, LAUNCH_DEXP)
+    }
+#undef LAUNCH_DEXP
     HIP_OK(hipGetLastError());
     return {dc_prev, dpool_dec, demb_dec};
 }

@@ -235,11 +235,53 @@ static inline at::Tensor nhwc_out(const at::Tensor& like, int64_t B,
                          .memory_format(at::MemoryFormat::ChannelsLast));
 }
 
-// split-K combine: element `off` summed over `splitk` fp32 slabs of n
+// split-K combine: element `off` summed over the fp32 slabs of n.
+//
+// S > 0 is the slab count at compile time: all S loads are issued before
+// the first add, so a thread pays one memory round trip, not S dependent
+// ones (the runtime-count loop compiles to load, wait, add per slab).
+// S == 0 is that runtime loop, for counts no planner produces.  Both add
+// in the order ((0 + s0) + s1) + ..., so every count gives the same bits
+// on either path.  Hosts pick S with SLAB_DISPATCH.
+constexpr int MAX_SLABS = 8;
+
+template <int S>
+__device__ __forceinline__ void load_slabs(const float* __restrict__ Yf,
+                                           int64_t n, int64_t off,
+                                           float (&s)[S > 0 ? S : 1]) {
+#pragma unroll
+    for (int k = 0; k < S; ++k) s[k] = Yf[k * n + off];
+}
+
+template <int S>
+__device__ __forceinline__ float add_slabs(const float (&s)[S > 0 ? S : 1]) {
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < S; ++k) v += s[k];
+    return v;
+}
+
+template <int S>
 __device__ __forceinline__ float sum_slabs(const float* __restrict__ Yf,
                                            int64_t n, int64_t off,
                                            int splitk) {
-    float v = 0.f;
-    for (int k = 0; k < splitk; ++k) v += Yf[k * n + off];
-    return v;
+    if constexpr (S > 0) {
+        float s[S];
+        load_slabs<S>(Yf, n, off, s);
+        return add_slabs<S>(s);
+    } else {
+        float v = 0.f;
+        for (int k = 0; k < splitk; ++k) v += Yf[k * n + off];
+        return v;
+    }
 }
+
+// CALL(S) with S = splitk for 1..MAX_SLABS, CALL(0) for any other count
+#define SLAB_DISPATCH(splitk, CALL) \
+    switch (splitk) { \
+        case 1: CALL(1); break; case 2: CALL(2); break; \
+        case 3: CALL(3); break; case 4: CALL(4); break; \
+        case 5: CALL(5); break; case 6: CALL(6); break; \
+        case 7: CALL(7); break; case 8: CALL(8); break; \
+        default: CALL(0); break; \
+    }

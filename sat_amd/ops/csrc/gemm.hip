@@ -177,7 +177,11 @@ void tiled_gemm_kernel(const bf16* __restrict__ A,    // [M,K]
 // partial sums into fp32 slab kq and a separate epilogue kernel combines
 // (an empty trailing chunk stores zeros).
 //
-// TANHA (slab mode, K % 32 == 0): the A operand is not read but built as
+// K % 32 == 0 (launch_skinny checks it), so no K tail exists; ragged M
+// and N are handled by clamped load rows and guarded stores, and the K
+// loop carries no edge test.
+//
+// TANHA (slab mode): the A operand is not read but built as
 // it loads, a = f2bf(Af * (1 - Ay^2)) from an fp32 gradient Af and the
 // bf16 tanh output Ay (what act_bwd_f32_out computes, same rounding);
 // wave 0 of the blockIdx.x == 0 blocks stores its K-chunk of it to Apre.
@@ -212,55 +216,79 @@ void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
     for (int i = 0; i < RF; ++i)
         acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
 
-    const bool wfull = (n0 + 16 <= N);
     if (active) {
-        for (int k = kbeg; k < kend; k += 32) {
-            const int kof = k + kgrp * 8;
-            bf16x8 b_frag = {};
-            if (kof + 8 <= K) {
-                int gb = n0 + lrow;
-                if (wfull || gb < N)
-                    b_frag = *(const bf16x8*)(W + (int64_t)gb * K + kof);
-            } else if (kof < K) {
-                int gb = n0 + lrow;
-                if (wfull || gb < N)
-                    for (int e = 0; e < 8 && kof + e < K; ++e)
-                        b_frag[e] = W[(int64_t)gb * K + kof + e];
+        // Rows past M / N are clamped onto the last valid one, not
+        // branched around: an MFMA output row depends on its own A row
+        // only (a column on its own W row), and the stores below drop
+        // them.  With no edge test left, the loads of a whole batch of
+        // K steps are issued before the first MFMA waits for one.
+        const bf16* wp = W + (int64_t)min(n0 + lrow, N - 1) * K + kgrp * 8;
+        int64_t aoff[RF];
+#pragma unroll
+        for (int mi = 0; mi < RF; ++mi)
+            aoff[mi] = (int64_t)min(mi * 16 + lrow, M - 1) * K + kgrp * 8;
+        const bool pre = TANHA && blockIdx.x == 0 && wave == 0;
+
+        // U consecutive 32-wide K steps from k: all loads, then the MFMAs
+        // in k order (each accumulator sums k-ascending, as one step at a
+        // time does)
+        auto steps = [&](auto uc, int k) {
+            constexpr int U = decltype(uc)::value;
+            bf16x8 bw[U], a[U][RF];
+            floatx4 g0[TANHA ? U : 1][RF], g1[TANHA ? U : 1][RF];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                bw[u] = *(const bf16x8*)(wp + k + u * 32);
+#pragma unroll
+                for (int mi = 0; mi < RF; ++mi) {
+                    const int64_t ao = aoff[mi] + k + u * 32;
+                    if constexpr (TANHA) {
+                        g0[u][mi] = *(const floatx4*)(Af + ao);
+                        g1[u][mi] = *(const floatx4*)(Af + ao + 4);
+                        a[u][mi] = *(const bf16x8*)(Ay + ao);
+                    } else {
+                        a[u][mi] = *(const bf16x8*)(A + ao);
+                    }
+                }
             }
 #pragma unroll
-            for (int mi = 0; mi < RF; ++mi) {
-                bf16x8 a0 = {};
-                int ar = mi * 16 + lrow;
-                if constexpr (TANHA) {
-                    if (ar < M) {
-                        const int64_t ao = (int64_t)ar * K + kof;
-                        floatx4 g0 = *(const floatx4*)(Af + ao);
-                        floatx4 g1 = *(const floatx4*)(Af + ao + 4);
-                        bf16x8 yv = *(const bf16x8*)(Ay + ao);
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int mi = 0; mi < RF; ++mi) {
+                    if constexpr (TANHA) {
+                        bf16x8 yv = a[u][mi];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             float y = bf2f(yv[e]);
-                            float g = e < 4 ? g0[e] : g1[e - 4];
+                            float g = e < 4 ? g0[u][mi][e]
+                                            : g1[u][mi][e - 4];
                             // y*y is exact in fp32 (bf16 operand), so
                             // contraction cannot move this result
-                            a0[e] = f2bf(g * (1.f - y * y));
+                            a[u][mi][e] = f2bf(g * (1.f - y * y));
                         }
-                        if (blockIdx.x == 0 && wave == 0)
-                            *(bf16x8*)(Apre + ao) = a0;
+                        if (pre && mi * 16 + lrow < M)
+                            *(bf16x8*)(Apre + aoff[mi] + k + u * 32)
+                                = a[u][mi];
                     }
-                } else
-                if (kof + 8 <= K) {
-                    if (ar < M)
-                        a0 = *(const bf16x8*)(A + (int64_t)ar * K + kof);
-                } else if (kof < K) {
-                    if (ar < M)
-                        for (int e = 0; e < 8 && kof + e < K; ++e)
-                            a0[e] = A[(int64_t)ar * K + kof + e];
+                    acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        a[u][mi], bw[u], acc[mi], 0, 0, 0);
                 }
-                acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    a0, b_frag, acc[mi], 0, 0, 0);
-            }
-        }
+        };
+
+        // batch depth: ~12 fragments in flight (8 for TANHA, whose A
+        // operand is three loads), so registers stay bounded at any K;
+        // a flagship split (2-6 steps) is one batch
+        constexpr int U = TANHA ? (RF >= 8 ? 1 : 8 / RF)
+                                : (RF >= 8 ? 2 : 12 / RF);
+        int k = kbeg;
+        for (; k + U * 32 <= kend; k += U * 32)
+            steps(std::integral_constant<int, U>{}, k);
+        if constexpr (U > 2)
+            for (; k + 64 <= kend; k += 64)
+                steps(std::integral_constant<int, 2>{}, k);
+        if constexpr (U > 1)
+            for (; k < kend; k += 32)
+                steps(std::integral_constant<int, 1>{}, k);
     }
 
     const int col = n0 + (lane & 15);
@@ -292,6 +320,7 @@ void skinny_gemm_kernel(const bf16* __restrict__ A,   // [M,K], M <= RF*16
 }
 
 // split-K combine + bias/act for both GEMM kernels' fp32 slabs
+template <int S>
 __global__ void skinny_epilogue_kernel(const float* __restrict__ Yf,
                                        const bf16* __restrict__ bias,
                                        bf16* __restrict__ Y,
@@ -299,8 +328,12 @@ __global__ void skinny_epilogue_kernel(const float* __restrict__ Yf,
                                        int splitk) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    float v = sum_slabs(Yf, n, idx, splitk);
-    if (bias != nullptr) v += bf2f(bias[idx % N]);
+    // the bias load goes out with the slab loads: always a valid address,
+    // the value is dropped when there is no bias
+    const bf16* bp = bias != nullptr ? bias + idx % N : (const bf16*)Yf;
+    float bv = bf2f(*bp);
+    float v = sum_slabs<S>(Yf, n, idx, splitk);
+    if (bias != nullptr) v += bv;
     Y[idx] = f2bf(apply_act(v, act));
 }
 
@@ -417,10 +450,14 @@ static void launch_tiled(hipStream_t stream, const at::Tensor& x,
 static void launch_epilogue(hipStream_t stream, const at::Tensor& yf,
                             const bf16* bias, at::Tensor& y, int act) {
     int64_t n = y.numel();
-    hipLaunchKernelGGL(skinny_epilogue_kernel, dim3(cdiv(n, 256)),
-                       dim3(256), 0, stream, (const float*)yf.data_ptr(),
-                       bias, (bf16*)y.data_ptr(), n, (int)y.size(1), act,
-                       (int)yf.size(0));
+    const int splitk = (int)yf.size(0);
+#define LAUNCH_EPI(S) \
+    hipLaunchKernelGGL(skinny_epilogue_kernel<S>, dim3(cdiv(n, 256)), \
+                       dim3(256), 0, stream, (const float*)yf.data_ptr(), \
+                       bias, (bf16*)y.data_ptr(), n, (int)y.size(1), act, \
+                       splitk)
+    SLAB_DISPATCH(splitk, LAUNCH_EPI)
+#undef LAUNCH_EPI
 }
 
 at::Tensor dense_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
@@ -497,15 +534,32 @@ at::Tensor dense_fwd(at::Tensor x, at::Tensor w, at::Tensor bias,
 
 // ---- GEMM + counter-hash dropout fused into the split-K epilogue ----
 
+template <int S>
 __global__ void skinny_epilogue_drop_kernel(
         const float* __restrict__ Yf, bf16* __restrict__ Y,
         const int64_t* __restrict__ seed_p, int64_t n, int splitk,
         float p, int salt) {
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    float v = sum_slabs(Yf, n, idx, splitk);
+    float v = sum_slabs<S>(Yf, n, idx, splitk);
     v *= drop_scale((uint32_t)(*seed_p), salt, (uint32_t)idx, p);
     Y[idx] = f2bf(v);
+}
+
+// y = bf16(sum of the yf slabs * dropout mask(salt))
+static void launch_epilogue_drop(hipStream_t stream, const at::Tensor& yf,
+                                 at::Tensor& y, const at::Tensor& seed,
+                                 double p, int64_t salt) {
+    int64_t n = y.numel();
+    const int splitk = (int)yf.size(0);
+#define LAUNCH_EPI(S) \
+    hipLaunchKernelGGL(skinny_epilogue_drop_kernel<S>, \
+                       dim3(cdiv(n, 256)), dim3(256), 0, stream, \
+                       (const float*)yf.data_ptr(), (bf16*)y.data_ptr(), \
+                       (const int64_t*)seed.data_ptr(), n, splitk, \
+                       (float)p, (int)salt)
+    SLAB_DISPATCH(splitk, LAUNCH_EPI)
+#undef LAUNCH_EPI
 }
 
 at::Tensor dense_fwd_drop(at::Tensor x, at::Tensor w, at::Tensor seed,
@@ -524,12 +578,7 @@ at::Tensor dense_fwd_drop(at::Tensor x, at::Tensor w, at::Tensor seed,
     auto y = at::empty({M, N}, x.options());
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
     auto yf = skinny_slabs(stream, x, w);
-    int64_t n = M * N;
-    hipLaunchKernelGGL(skinny_epilogue_drop_kernel,
-                       dim3(cdiv(n, 256)), dim3(256), 0, stream,
-                       (const float*)yf.data_ptr(), (bf16*)y.data_ptr(),
-                       (const int64_t*)seed.data_ptr(), n,
-                       (int)yf.size(0), (float)p, (int)salt);
+    launch_epilogue_drop(stream, yf, y, seed, p, salt);
     HIP_OK(hipGetLastError());
     return y;
 }
@@ -542,13 +591,8 @@ at::Tensor slab_epilogue_drop(at::Tensor yf, at::Tensor seed, double p,
     TORCH_CHECK(yf.dim() == 3, "slabs must be [splitk, M, N]");
     auto y = at::empty({yf.size(1), yf.size(2)},
                        yf.options().dtype(at::kBFloat16));
-    int64_t n = y.numel();
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
-    hipLaunchKernelGGL(skinny_epilogue_drop_kernel,
-                       dim3(cdiv(n, 256)), dim3(256), 0, stream,
-                       (const float*)yf.data_ptr(), (bf16*)y.data_ptr(),
-                       (const int64_t*)seed.data_ptr(), n,
-                       (int)yf.size(0), (float)p, (int)salt);
+    launch_epilogue_drop(stream, yf, y, seed, p, salt);
     HIP_OK(hipGetLastError());
     return y;
 }
@@ -557,18 +601,39 @@ at::Tensor slab_epilogue_drop(at::Tensor yf, at::Tensor seed, double p,
 
 // the four pre-activation gates of (b, hh): split-K sum + bias, written
 // to gates[] as bf16 (saved for backward) and returned in fp32
+//
+// The 4*S slab loads, the 4 bias loads and c_prev[b, hh] (returned in
+// cp) all go out before the first add.  The bias address is valid with
+// or without a bias (the value is dropped without one), so no load sits
+// behind a branch.  4*B*H < 2^31 (the hosts check it).
+template <int S>
 __device__ __forceinline__ void sum_gates(const float* __restrict__ Yf,
                                           const bf16* __restrict__ bias,
+                                          const bf16* __restrict__ c_prev,
                                           bf16* __restrict__ gates,
                                           int B, int H, int b, int hh,
-                                          int splitk, float g[4]) {
-    int64_t n = (int64_t)B * 4 * H;
+                                          int splitk, float g[4],
+                                          float& cp) {
+    const int n = B * 4 * H;
+    const int off0 = b * 4 * H + hh;
+    const bf16* bp = bias != nullptr ? bias + hh : c_prev;
+    const int bstride = bias != nullptr ? H : 0;
+    float s[4][S > 0 ? S : 1];
+    bf16 bv[4];
+    if constexpr (S > 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) load_slabs<S>(Yf, n, off0 + q * H, s[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) bv[q] = bp[q * bstride];
+    cp = bf2f(c_prev[b * H + hh]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        int64_t off = (int64_t)b * 4 * H + q * H + hh;
-        float acc = sum_slabs(Yf, n, off, splitk);
-        if (bias != nullptr) acc += bf2f(bias[q * H + hh]);
-        gates[off] = f2bf(acc);
+        float acc;
+        if constexpr (S > 0) acc = add_slabs<S>(s[q]);
+        else acc = sum_slabs<0>(Yf, n, off0 + q * H, splitk);
+        if (bias != nullptr) acc += bf2f(bv[q]);
+        gates[off0 + q * H] = f2bf(acc);
         g[q] = acc;
     }
 }
@@ -576,6 +641,7 @@ __device__ __forceinline__ void sum_gates(const float* __restrict__ Yf,
 // gates epilogue + LSTM pointwise: thread per (b,h) sums the 4 gate
 // elements across split-K slabs, applies the LSTM gate math, writes the
 // bf16 gates plus h_raw and c_new.
+template <int S>
 __global__ void skinny_epi_lstm_kernel(const float* __restrict__ Yf,
                                        const bf16* __restrict__ bias,
                                        const bf16* __restrict__ c_prev,
@@ -586,9 +652,10 @@ __global__ void skinny_epi_lstm_kernel(const float* __restrict__ Yf,
                                        float fb) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * H) return;
-    float g[4], cn, h;
-    sum_gates(Yf, bias, gates, B, H, idx / H, idx % H, splitk, g);
-    lstm_cell_fwd(g, bf2f(c_prev[idx]), fb, cn, h);
+    float g[4], cp, cn, h;
+    sum_gates<S>(Yf, bias, c_prev, gates, B, H, idx / H, idx % H, splitk,
+                 g, cp);
+    lstm_cell_fwd(g, cp, fb, cn, h);
     h_out[idx] = f2bf(h);
     c_out[idx] = f2bf(cn);
 }
@@ -604,15 +671,19 @@ std::vector<at::Tensor> dense_lstm_fwd(at::Tensor xh, at::Tensor wl,
     auto h_out = at::empty_like(c_prev);
     auto c_out = at::empty_like(c_prev);
     hipStream_t s = at::cuda::getCurrentCUDAStream();
+    TORCH_CHECK(M * N < (1LL << 31), "gates have >= 2^31 elements");
     auto yf = skinny_slabs(s, xh, wl);
-    hipLaunchKernelGGL(skinny_epi_lstm_kernel,
-                       dim3(cdiv(B * H, 256)), dim3(256), 0, s,
-                       (const float*)yf.data_ptr(),
-                       (const bf16*)bl.data_ptr(),
-                       (const bf16*)c_prev.data_ptr(),
-                       (bf16*)gates.data_ptr(), (bf16*)h_out.data_ptr(),
-                       (bf16*)c_out.data_ptr(), B, H, (int)yf.size(0),
-                       (float)fb);
+    const int splitk = (int)yf.size(0);
+#define LAUNCH_EPI(S) \
+    hipLaunchKernelGGL(skinny_epi_lstm_kernel<S>, \
+                       dim3(cdiv(B * H, 256)), dim3(256), 0, s, \
+                       (const float*)yf.data_ptr(), \
+                       (const bf16*)bl.data_ptr(), \
+                       (const bf16*)c_prev.data_ptr(), \
+                       (bf16*)gates.data_ptr(), (bf16*)h_out.data_ptr(), \
+                       (bf16*)c_out.data_ptr(), B, H, splitk, (float)fb)
+    SLAB_DISPATCH(splitk, LAUNCH_EPI)
+#undef LAUNCH_EPI
     HIP_OK(hipGetLastError());
     return {gates, h_out, c_out};
 }
@@ -741,6 +812,7 @@ void dense_glds_kernel(const bf16* __restrict__ A,   // [M,K]
 // Removes one launch + the dxh round trip per decoder reverse step.
 // ---------------------------------------------------------------------
 
+template <int S>
 __global__ void skinny_epi_dx_kernel(const float* __restrict__ Yf,
                                      const bf16* __restrict__ dpool_dec,
                                      const bf16* __restrict__ demb_dec,
@@ -748,26 +820,34 @@ __global__ void skinny_epi_dx_kernel(const float* __restrict__ Yf,
                                      bf16* __restrict__ dpooled,
                                      bf16* __restrict__ demb_out,
                                      bf16* __restrict__ dsth,
-                                     int64_t n, int splitk,
+                                     int n, int splitk,
                                      int B, int D, int E, int H,
                                      float p, int salt) {
     const uint32_t seed = (uint32_t)(*seed_p);
     const int I = D + E;
     const int W = I + H;
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    float g = sum_slabs(Yf, n, idx, splitk);
-    int b = (int)(idx / W), j = (int)(idx % W);
+    int b = idx / W, j = idx - b * W;
+    // the decoder-side addend goes out with the slab loads, selected by
+    // address (the H range reads a valid element it does not use)
+    const bf16* addp = j < D ? dpool_dec + b * D + j
+                     : j < I ? demb_dec + b * E + (j - D)
+                             : (const bf16*)Yf;
+    float add = bf2f(*addp);
+    float g = sum_slabs<S>(Yf, n, idx, splitk);
     if (j < I) {
+        // the mask multiply and the add each round on their own, as they
+        // did while the addend was loaded after the multiply; with it
+        // already in a register the compiler would fuse them into an FMA
+#pragma clang fp contract(off)
         g *= drop_scale(seed, salt, (uint32_t)(b * I + j), p);
         if (j < D)
-            dpooled[(int64_t)b * D + j] =
-                f2bf(g + bf2f(dpool_dec[(int64_t)b * D + j]));
+            dpooled[b * D + j] = f2bf(g + add);
         else
-            demb_out[(int64_t)b * E + (j - D)] =
-                f2bf(g + bf2f(demb_dec[(int64_t)b * E + (j - D)]));
+            demb_out[b * E + (j - D)] = f2bf(g + add);
     } else {
-        dsth[(int64_t)b * H + (j - I)] = f2bf(g);
+        dsth[b * H + (j - I)] = f2bf(g);
     }
 }
 
@@ -787,17 +867,22 @@ std::vector<at::Tensor> dense_dx_fuse(at::Tensor dgates, at::Tensor wl_t,
     hipStream_t stream = at::cuda::getCurrentCUDAStream();
     auto yf = skinny_slabs(stream, dgates, wl_t);
     int64_t n = M * N;
-    hipLaunchKernelGGL(skinny_epi_dx_kernel, dim3(cdiv(n, 256)),
-                       dim3(256), 0, stream,
-                       (const float*)yf.data_ptr(),
-                       (const bf16*)dpool_dec.data_ptr(),
-                       (const bf16*)demb_dec.data_ptr(),
-                       (const int64_t*)seed.data_ptr(),
-                       (bf16*)dpooled.data_ptr(),
-                       (bf16*)demb_out.data_ptr(),
-                       (bf16*)dsth.data_ptr(),
-                       n, (int)yf.size(0), (int)M, (int)D, (int)E, (int)H,
-                       (float)p, (int)salt);
+    TORCH_CHECK(n < (1LL << 31), "dxh has >= 2^31 elements");
+    const int splitk = (int)yf.size(0);
+#define LAUNCH_EPI(S) \
+    hipLaunchKernelGGL(skinny_epi_dx_kernel<S>, dim3(cdiv(n, 256)), \
+                       dim3(256), 0, stream, \
+                       (const float*)yf.data_ptr(), \
+                       (const bf16*)dpool_dec.data_ptr(), \
+                       (const bf16*)demb_dec.data_ptr(), \
+                       (const int64_t*)seed.data_ptr(), \
+                       (bf16*)dpooled.data_ptr(), \
+                       (bf16*)demb_out.data_ptr(), \
+                       (bf16*)dsth.data_ptr(), \
+                       (int)n, splitk, (int)M, (int)D, (int)E, (int)H, \
+                       (float)p, (int)salt)
+    SLAB_DISPATCH(splitk, LAUNCH_EPI)
+#undef LAUNCH_EPI
     HIP_OK(hipGetLastError());
     return {dpooled, dsth};
 }
@@ -817,6 +902,7 @@ std::vector<at::Tensor> dense_dx_fuse(at::Tensor dgates, at::Tensor wl_t,
 // pooled columns [0, D) come from the next step's attn_pool_fwd_xh).
 // ---------------------------------------------------------------------
 
+template <int S, bool XN>   // S: slab count (common.h); XN: xh_next given
 __global__ void skinny_epi_lstm_expand_kernel(
         const float* __restrict__ Yf, const bf16* __restrict__ bias,
         const bf16* __restrict__ c_prev,
@@ -834,35 +920,44 @@ __global__ void skinny_epi_lstm_expand_kernel(
     const uint32_t seed = (uint32_t)(*seed_p);
     const int W = H + D + E;
     const int I = D + E;
-    int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (int64_t)B * W) return;
-    int b = idx / W, j = idx % W;
+    // B * W and 4 * B * H < 2^31 (the host checks it)
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * W) return;
+    int b = idx / W, j = idx - b * W;
     float val;
     if (j < H) {
-        float g[4], cn, h;
-        sum_gates(Yf, bias, gates, B, H, b, j, splitk, g);
-        lstm_cell_fwd(g, bf2f(c_prev[(int64_t)b * H + j]), fb, cn, h);
-        c_out[(int64_t)b * H + j] = f2bf(cn);
+        float g[4], cp, cn, h;
+        sum_gates<S>(Yf, bias, c_prev, gates, B, H, b, j, splitk, g, cp);
+        lstm_cell_fwd(g, cp, fb, cn, h);
+        c_out[b * H + j] = f2bf(cn);
         uint32_t hidx = (uint32_t)(b * H + j);
         float ot = h * drop_scale(seed, s + 4, hidx, p_lstm);
         bf16 sth = f2bf(h * drop_scale(seed, s + 5, hidx, p_lstm));
-        sth_t[(int64_t)b * H + j] = sth;
-        if (xh_next != nullptr)
-            xh_next[(int64_t)b * W + I + j] = sth;
+        sth_t[b * H + j] = sth;
+        if constexpr (XN)
+            xh_next[b * W + I + j] = sth;
         if (od_next != nullptr)
-            od_next[(int64_t)b * H + j] =
+            od_next[b * H + j] =
                 f2bf(ot * drop_scale(seed, s + 16 + 1, hidx, p_fc));
         val = ot;
     } else if (j < H + D) {
-        val = bf2f(pooled[(int64_t)b * D + (j - H)]);
+        val = bf2f(pooled[b * D + (j - H)]);
     } else {
+        // both id loads first, then both table gathers: two round trips,
+        // not four (XN is a template parameter so that no load waits
+        // behind a test of xh_next)
         int e = j - H - D;
-        val = bf2f(table[ids[b] * E + e]);
-        if (xh_next != nullptr)
-            xh_next[(int64_t)b * W + D + e] =
-                f2bf(bf2f(table[next_ids[b] * E + e])
+        int64_t id = ids[b], nid = 0;
+        if constexpr (XN) nid = next_ids[b];
+        bf16 tv = table[id * E + e];
+        if constexpr (XN) {
+            bf16 tn = table[nid * E + e];
+            xh_next[b * W + D + e] =
+                f2bf(bf2f(tn)
                      * drop_scale(seed, s + 16 + 3,
                                   (uint32_t)(b * I + D + e), p_lstm));
+        }
+        val = bf2f(tv);
     }
     expdrop[idx] = f2bf(val * drop_scale(seed, s + 6,
                                          (uint32_t)(b * W + j), p_fc));
@@ -890,21 +985,29 @@ static std::vector<at::Tensor> dense_lstm_expand_impl(
     if (od_next.defined() && od_next.numel() > 0)
         od_ptr = (bf16*)od_next.data_ptr();
     int64_t n = (int64_t)B * (H + D + E);
-    hipLaunchKernelGGL(skinny_epi_lstm_expand_kernel,
-                       dim3(cdiv(n, 256)), dim3(256), 0, stream,
-                       (const float*)yf.data_ptr(), bias_ptr,
-                       (const bf16*)c_prev.data_ptr(),
-                       (const bf16*)pooled.data_ptr(),
-                       (const bf16*)table.data_ptr(),
-                       (const int64_t*)ids.data_ptr(),
-                       (const int64_t*)seed.data_ptr(),
-                       (bf16*)gates.data_ptr(),
-                       (bf16*)c_out.data_ptr(),
-                       (bf16*)sth_t.data_ptr(),
-                       (bf16*)expdrop.data_ptr(), od_ptr,
-                       B, H, D, E, (int)yf.size(0),
-                       (float)fb, (float)p_lstm, (float)p_fc, (int)s,
-                       next_ids_ptr, xh_next_ptr);
+    TORCH_CHECK(n < (1LL << 31) && M * N < (1LL << 31),
+                "expand row or gates have >= 2^31 elements");
+    const int splitk = (int)yf.size(0);
+#define LAUNCH_EPI(S) \
+    hipLaunchKernelGGL((xh_next_ptr != nullptr \
+                            ? skinny_epi_lstm_expand_kernel<S, true> \
+                            : skinny_epi_lstm_expand_kernel<S, false>), \
+                       dim3(cdiv(n, 256)), dim3(256), 0, stream, \
+                       (const float*)yf.data_ptr(), bias_ptr, \
+                       (const bf16*)c_prev.data_ptr(), \
+                       (const bf16*)pooled.data_ptr(), \
+                       (const bf16*)table.data_ptr(), \
+                       (const int64_t*)ids.data_ptr(), \
+                       (const int64_t*)seed.data_ptr(), \
+                       (bf16*)gates.data_ptr(), \
+                       (bf16*)c_out.data_ptr(), \
+                       (bf16*)sth_t.data_ptr(), \
+                       (bf16*)expdrop.data_ptr(), od_ptr, \
+                       B, H, D, E, splitk, \
+                       (float)fb, (float)p_lstm, (float)p_fc, (int)s, \
+                       next_ids_ptr, xh_next_ptr)
+    SLAB_DISPATCH(splitk, LAUNCH_EPI)
+#undef LAUNCH_EPI
     HIP_OK(hipGetLastError());
     return {gates, c_out, sth_t};
 }

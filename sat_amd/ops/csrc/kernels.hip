@@ -252,11 +252,22 @@ std::vector<at::Tensor> attn_scores_fused(at::Tensor t1, at::Tensor t2,
 // per row, coalesced), plus dctx = α ⊗ dpooled for the same rows.
 // phase 2, grid (B): dlogits = α (dα_ext + s − Σ_l α·(dα_ext + s)).
 
-__global__ void attn_pool_bwd_p1_kernel(
+//
+// A wave takes its rows (l0 + wid, step 4) in batches of 8 with the alpha
+// and ctx loads of the whole batch issued before the first use (one row
+// at a time was two dependent round trips per row).  A row past the chunk
+// end loads the chunk's last row, is computed and not stored: a branch
+// around the whole row would let the compiler move the row's loads down
+// into it, one wait per row again.  DCTX: dctx is wanted.
+
+template <bool DCTX>
+__global__ __launch_bounds__(256)
+void attn_pool_bwd_p1_kernel(
         const bf16* __restrict__ ctx, const float* __restrict__ alpha,
         const bf16* __restrict__ dpooled,
         float* __restrict__ sbuf, bf16* __restrict__ dctx,
         int L, int D) {
+    constexpr int R = 8;
     int b = blockIdx.x;
     int nchunk = gridDim.y;
     int lchunk = (L + nchunk - 1) / nchunk;
@@ -266,30 +277,43 @@ __global__ void attn_pool_bwd_p1_kernel(
     const bf16* cb = ctx + (int64_t)b * L * D;
     const bf16* dp = dpooled + (int64_t)b * D;
 
-    for (int l = l0 + wid; l < l1; l += 4) {
-        float acc = 0.f;
-        float a = alpha[(int64_t)b * L + l];
+    for (int lb = l0 + wid; lb < l1; lb += 4 * R) {
+        float a[R], acc[R];
+        const bf16* cr[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int l = min(lb + 4 * r, l1 - 1);
+            a[r] = alpha[(int64_t)b * L + l];
+            cr[r] = cb + (int64_t)l * D;
+            acc[r] = 0.f;
+        }
         for (int d0 = lane * 8; d0 + 8 <= D; d0 += 64 * 8) {
-            bf16x8 cv = *(const bf16x8*)(cb + (int64_t)l * D + d0);
+            bf16x8 cv[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                cv[r] = *(const bf16x8*)(cr[r] + d0);
             bf16x8 dv = *(const bf16x8*)(dp + d0);
-            if (dctx != nullptr) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
                 bf16x8 out;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     float dpe = bf2f(dv[e]);
-                    acc += bf2f(cv[e]) * dpe;
-                    out[e] = f2bf(a * dpe);
+                    acc[r] += bf2f(cv[r][e]) * dpe;
+                    if constexpr (DCTX) out[e] = f2bf(a[r] * dpe);
                 }
-                *(bf16x8*)(dctx + (int64_t)b * L * D + (int64_t)l * D + d0)
-                    = out;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    acc += bf2f(cv[e]) * bf2f(dv[e]);
+                if constexpr (DCTX) {
+                    if (lb + 4 * r < l1)
+                        *(bf16x8*)(dctx + (cr[r] - ctx) + d0) = out;
+                }
             }
         }
-        acc = wave_sum(acc);
-        if (lane == 0) sbuf[(int64_t)b * L + l] = acc;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float s = wave_sum(acc[r]);
+            if (lane == 0 && lb + 4 * r < l1)
+                sbuf[(int64_t)b * L + lb + 4 * r] = s;
+        }
     }
 }
 
@@ -300,11 +324,16 @@ __global__ void attn_pool_bwd_p2_kernel(
     __shared__ float red[4];
     int b = blockIdx.x;
     int tid = threadIdx.x;
+    // the dalpha load goes out with the other two: its address is valid
+    // with or without a dalpha (the value is dropped without one)
+    const float* dap = dalpha != nullptr ? dalpha : sbuf;
     float part = 0.f;
     for (int l = tid; l < L; l += blockDim.x) {
         float da = sbuf[(int64_t)b * L + l];
-        if (dalpha != nullptr) da += dalpha[(int64_t)b * L + l];
-        part += alpha[(int64_t)b * L + l] * da;
+        float dx = dap[(int64_t)b * L + l];
+        float al = alpha[(int64_t)b * L + l];
+        if (dalpha != nullptr) da += dx;
+        part += al * da;
     }
     part = wave_sum(part);
     if ((tid & 63) == 0) red[tid >> 6] = part;
@@ -312,9 +341,10 @@ __global__ void attn_pool_bwd_p2_kernel(
     float dot = red[0] + red[1] + red[2] + red[3];
     for (int l = tid; l < L; l += blockDim.x) {
         float da = sbuf[(int64_t)b * L + l];
-        if (dalpha != nullptr) da += dalpha[(int64_t)b * L + l];
-        dlogits[(int64_t)b * L + l] =
-            alpha[(int64_t)b * L + l] * (da - dot);
+        float dx = dap[(int64_t)b * L + l];
+        float al = alpha[(int64_t)b * L + l];
+        if (dalpha != nullptr) da += dx;
+        dlogits[(int64_t)b * L + l] = al * (da - dot);
     }
 }
 
@@ -342,7 +372,9 @@ std::vector<at::Tensor> attn_pool_bwd(at::Tensor ctx, at::Tensor alpha,
     // NOTE: a one-block-per-image fused p1+p2 variant measured SLOWER at
     // batch 32 — it cuts the p1 grid from B*4 to B blocks on a
     // latency-bound chain; the two-launch form stays (r02 A/B evidence).
-    hipLaunchKernelGGL(attn_pool_bwd_p1_kernel, dim3(B, 8), dim3(256), 0, s,
+    hipLaunchKernelGGL((need_dctx ? attn_pool_bwd_p1_kernel<true>
+                                  : attn_pool_bwd_p1_kernel<false>),
+                       dim3(B, 8), dim3(256), 0, s,
                        (const bf16*)ctx.data_ptr(),
                        (const float*)alpha.data_ptr(),
                        (const bf16*)dpooled.data_ptr(),
