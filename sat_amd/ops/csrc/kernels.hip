@@ -735,6 +735,7 @@ static std::vector<at::Tensor> attn_pool_fwd_impl(
     CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_F32(logits);
     int B = ctx.size(0), L = ctx.size(1), D = ctx.size(2);
     TORCH_CHECK(L <= MAX_L, "attention locations exceed LDS stage");
+    TORCH_CHECK(D % 8 == 0, "attn_pool_fwd requires D % 8 == 0");
     TORCH_CHECK(logits.numel() == (int64_t)B * L);
     auto alpha = at::empty({B, L}, ctx.options().dtype(at::kFloat));
     auto pooled = at::empty({B, D}, ctx.options());
@@ -813,6 +814,7 @@ at::Tensor embedding_fwd(at::Tensor ids, at::Tensor table) {
 
 at::Tensor embedding_bwd(at::Tensor ids, at::Tensor dy, int64_t rows) {
     CHECK_GPU(ids); CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_BF16(dy);
+    TORCH_CHECK(ids.scalar_type() == at::kLong, "ids must be int64");
     int B = ids.numel(), E = dy.size(1);
     auto dtable = at::zeros({rows, E}, dy.options().dtype(at::kFloat));
     hipStream_t s = at::cuda::getCurrentCUDAStream();
@@ -884,6 +886,7 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor labels,
                                at::Tensor mask) {
     CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
     CHECK_GPU(labels); CHECK_GPU(mask); CHECK_F32(mask);
+    TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
     int B = logits.size(0), V = logits.size(1);
     auto losses = at::empty({B}, logits.options().dtype(at::kFloat));
     auto lse = at::empty({B}, logits.options().dtype(at::kFloat));
@@ -900,6 +903,7 @@ std::vector<at::Tensor> ce_fwd(at::Tensor logits, at::Tensor labels,
 at::Tensor ce_bwd(at::Tensor logits, at::Tensor labels, at::Tensor mask,
                   at::Tensor lse, at::Tensor dloss) {
     CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
+    TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
     int B = logits.size(0), V = logits.size(1);
     auto dlogits = at::empty_like(logits);
     hipStream_t s = at::cuda::getCurrentCUDAStream();

@@ -75,11 +75,21 @@ class Optimizer(object):
         cfg = self.config
         self.step_count += 1
         lr = self.learning_rate()
+        use_hip = (len(self.params) > 0 and self.params[0].is_cuda
+                   and self.kind == 'Adam')
+        if use_hip:
+            # the fused kernel walks p/g/m/v in flat storage order and m/v
+            # are laid out like p, so a grad in another layout (a
+            # contiguous grad assigned to a channels_last weight) would
+            # pair the wrong elements: lay it out like its parameter, once
+            # (autograd then accumulates into that tensor in place)
+            for p in self.params:
+                g = p.grad
+                if g is not None and g.stride() != p.stride():
+                    p.grad = torch.empty_like(p, dtype=g.dtype).copy_(g)
         grads = [p.grad if p.grad is not None else torch.zeros_like(p)
                  for p in self.params]
 
-        use_hip = (len(self.params) > 0 and self.params[0].is_cuda
-                   and self.kind == 'Adam')
         if use_hip:
             from sat_amd import _C
             from .ops import hip
@@ -118,9 +128,10 @@ class Optimizer(object):
                 # float4 path needs every tensor boundary 16B-aligned
                 self._mt_vec4 = all(c % 4 == 0 for c in cum)
                 for g, p0 in zip(grads, self.params):
-                    # dense storage in any layout (channels_last conv
-                    # grads included) is fine: p/g/m/v share the layout
-                    # and the kernel iterates flat storage order
+                    # dense storage in either layout (channels_last conv
+                    # grads included) is fine: g has p's strides by now,
+                    # m/v were allocated like p, and the kernel iterates
+                    # flat storage order
                     if g.dtype != torch.float32 or not (
                             g.is_contiguous()
                             or g.is_contiguous(
