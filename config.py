@@ -112,6 +112,11 @@ class Config(object):
         self.synthetic_data = False      # synthetic COCO-shaped data (no files)
         self.synthetic_num_images = 640
         self.seed = 1234
+        self.use_fused_optimizer = True  # RMSProp / Momentum / SGD through
+        #                                  the chunk-table HIP kernels (graph-
+        #                                  capturable; False = eager PyTorch
+        #                                  math with host syncs).  Adam is
+        #                                  always fused on the GPU.
 
         # Optional JSON overrides from the environment (testing / ops
         # hook): SAT_CONFIG_OVERRIDES='{"batch_size": 2, ...}'

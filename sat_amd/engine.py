@@ -4,7 +4,7 @@ The reference amortizes per-op dispatch by building one static TF graph and
 letting the C++ runtime execute it.  The MI355X-native
 equivalent is hipGraph capture: the whole training step — CNN forward,
 20-step attention-LSTM forward, backward, bucketed all-reduce (DP) and the
-fused Adam — is captured once into a hipGraph and replayed per step, so the
+fused optimizer — is captured once into a hipGraph and replayed per step, so the
 ~1500 kernel launches cost one graph launch instead of ~1500 dispatches.
 
 Requirements made true elsewhere:
@@ -37,10 +37,8 @@ class GraphedTrainStep(object):
     def _inner(self, images, sentences, masks):
         out = self.model(images, sentences, masks)
         opt = self.optimizer
-        fused = (opt.kind == 'Adam' and len(opt.params) > 0
-                 and opt.params[0].is_cuda)
-        if not fused:
-            # the fused Adam zeroes grads inside its own update kernel
+        if not opt.fused:
+            # the fused optimizer zeroes grads inside its own update kernel
             for p in opt.params:
                 if p.grad is not None:
                     p.grad.zero_()
@@ -89,9 +87,7 @@ class GraphedTrainStep(object):
         split mode (collectives and optimizer stay outside)."""
         out = self.model(images, sentences, masks)
         opt = self.optimizer
-        fused = (opt.kind == 'Adam' and len(opt.params) > 0
-                 and opt.params[0].is_cuda)
-        if not fused:
+        if not opt.fused:
             for p in opt.params:
                 if p.grad is not None:
                     p.grad.zero_()
@@ -121,7 +117,7 @@ class GraphedTrainStep(object):
     def _capture_split(self, images, sentences, masks):
         """Split mode: capture fwd+bwd (including the DDP bucket
         fill/scale kernels) in one graph; RCCL collectives + the fused
-        Adam run eagerly after each replay.  Used when full capture
+        optimizer run eagerly after each replay.  Used when full capture
         fails at world > 1 (e.g. a collective that cannot be captured):
         keeps ~99% of the launches in the graph without putting RCCL
         inside it."""

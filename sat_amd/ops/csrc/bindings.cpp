@@ -133,6 +133,14 @@ void adam_step(std::vector<at::Tensor> params, std::vector<at::Tensor> grads,
                at::Tensor step_dev, double lr0, double decay_factor,
                double steps_per_decay, double b1, double b2, double eps,
                double clip, at::Tensor gsq);
+// chunk-table SGD / Momentum / RMSProp (optim_mt.hip)
+void sq_norm_chunks(at::Tensor chunks, at::Tensor ptrs, at::Tensor vec,
+                    at::Tensor partials);
+void opt_step_mt(at::Tensor chunks, at::Tensor ptrs, at::Tensor vec,
+                 bool any_vec, at::Tensor step_dev, double lr0,
+                 double decay_factor, double steps_per_decay,
+                 double momentum, double decay, double eps, double clip,
+                 int64_t kind, bool zero_grads, at::Tensor partials);
 
 // per-step chain fusions of the decoder BPTT (sat_amd/models/bptt.py)
 std::vector<at::Tensor> attn_scores_bwd_step(
@@ -230,6 +238,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sq_norm_mt", &sq_norm_mt);
     m.def("adam_step_mt", &adam_step_mt);
     m.def("adam_step", &adam_step);
+    m.def("sq_norm_chunks", &sq_norm_chunks);
+    m.def("opt_step_mt", &opt_step_mt);
     m.def("attn_scores_bwd_step", &attn_scores_bwd_step,
           "attn_scores_bwd_tanh into a caller-zeroed dt2 slice");
     m.def("attn_pool_fwd_xh", &attn_pool_fwd_xh,

@@ -6,16 +6,49 @@ Supports 'Adam' (default; β1/β2/ε from config, config.py:41-43), 'RMSProp',
 config.clip_gradients (model.py:510) and the optional staircase exponential
 LR decay (model.py:466-474, inactive at the default decay factor 1.0).
 
-On GPU the Adam path runs two hand-written CDNA4 kernels per step
-(sat_amd/ops/csrc/adam.hip): a multi-tensor grad-norm² reduction and a
-multi-tensor clip+Adam update — one launch each over all ~14M decoder params
-instead of per-tensor eager ops.  Other optimizers use PyTorch-ROCm eager
-math (parity features, not the flagship path).
+On GPU every kind runs two hand-written CDNA4 kernels per step, a
+multi-tensor grad-norm² reduction and a multi-tensor clip+update — one
+launch each over all ~14M decoder params instead of per-tensor eager ops,
+with the step counter, the LR staircase and the clip scale on the device,
+so the step has no host sync and is hipGraph-capturable:
+
+  * Adam: sq_norm_mt + adam_step_mt (sat_amd/ops/csrc/kernels.hip), over
+    the concatenation of all tensors;
+  * RMSProp, Momentum, SGD: sq_norm_chunks + opt_step_mt
+    (sat_amd/ops/csrc/optim_mt.hip), over a host-built table of chunks of
+    MT_CHUNK elements that never cross a tensor.  `use_fused_optimizer =
+    False` sends these three down the eager path instead.
+
+The eager path (PyTorch math, one host sync per tensor for the norm) serves
+the CPU.
 """
 
 import math
 
 import torch
+
+# elements per chunk of the chunk-table kernels: one float4 per thread of a
+# 256-thread block, and small enough that the ~14M flagship elements give
+# each of the 2048 blocks 6 or 7 chunks (an uneven last round costs 1/7)
+MT_CHUNK = 1024
+
+FUSED_KINDS = ('Adam', 'RMSProp', 'Momentum', 'SGD')
+# kernel codes of optim_mt.hip
+_K_SGD, _K_MOM, _K_NAG, _K_RMS, _K_RMSC = range(5)
+
+
+def build_chunk_table(numels, chunk=MT_CHUNK):
+    """Cut tensors of `numels` elements into (tensor, start, count) chunks
+    of at most `chunk` elements, in tensor order.  No chunk crosses a
+    tensor, every start is a multiple of 4 (chunk is), and only the last
+    chunk of a tensor may be short."""
+    if chunk <= 0 or chunk % 4:
+        raise ValueError('chunk must be a positive multiple of 4')
+    table = []
+    for t, n in enumerate(numels):
+        for start in range(0, n, chunk):
+            table.append((t, start, min(chunk, n - start)))
+    return table
 
 
 class Optimizer(object):
@@ -48,12 +81,22 @@ class Optimizer(object):
                 self.step_count // cfg.num_steps_per_decay)
         return lr
 
+    @property
+    def fused(self):
+        """step() runs the fused HIP kernels (and zeroes grads itself)"""
+        if not self.params or not self.params[0].is_cuda:
+            return False
+        if self.kind == 'Adam':
+            return True
+        return (self.kind in FUSED_KINDS and bool(
+            getattr(self.config, 'use_fused_optimizer', True)))
+
     def zero_grad(self):
         for p in self.params:
             p.grad = None
 
     # ---- bf16 shadow weights ----
-    # The fused Adam refreshes persistent bf16 copies of registered
+    # The fused kernels refresh persistent bf16 copies of registered
     # params in its own update pass (free — the new value is already in
     # a register), so the compute path reads shadows instead of casting
     # weights every forward.  Non-fused/eager steps fall back to an
@@ -63,6 +106,7 @@ class Optimizer(object):
         """mapping: {param: bf16 tensor of the same shape}."""
         self._shadows = dict(mapping)
         self._mt_ptrs = None  # force desc rebuild
+        self._ck_ptrs = None
         self.sync_shadows()
 
     def sync_shadows(self):
@@ -75,9 +119,9 @@ class Optimizer(object):
         cfg = self.config
         self.step_count += 1
         lr = self.learning_rate()
-        use_hip = (len(self.params) > 0 and self.params[0].is_cuda
-                   and self.kind == 'Adam')
-        if use_hip:
+        fused = self.fused
+        use_hip = fused and self.kind == 'Adam'
+        if fused:
             # the fused kernel walks p/g/m/v in flat storage order and m/v
             # are laid out like p, so a grad in another layout (a
             # contiguous grad assigned to a channels_last weight) would
@@ -87,6 +131,8 @@ class Optimizer(object):
                 g = p.grad
                 if g is not None and g.stride() != p.stride():
                     p.grad = torch.empty_like(p, dtype=g.dtype).copy_(g)
+        if fused and not use_hip:
+            return self._step_chunks()
         grads = [p.grad if p.grad is not None else torch.zeros_like(p)
                  for p in self.params]
 
@@ -155,7 +201,7 @@ class Optimizer(object):
                 getattr(self, '_mt_vec4', False))
             return
 
-        # ---- eager path (CPU, or non-Adam optimizers) ----
+        # ---- eager path (CPU, or use_fused_optimizer = False) ----
         gnorm = math.sqrt(sum(float((g.float() ** 2).sum()) for g in grads))
         scale = 1.0
         if cfg.clip_gradients and gnorm > cfg.clip_gradients:
@@ -194,6 +240,94 @@ class Optimizer(object):
                 raise ValueError('unknown optimizer %r' % (self.kind,))
             p.data.add_(upd.to(p.dtype), alpha=-lr)
         self.sync_shadows()
+
+    def _step_chunks(self):
+        """RMSProp / Momentum / SGD through optim_mt.hip: two launches (one
+        without clipping) and the counter's add_, no host sync, nothing
+        allocated after the first call.  The slots are the tensors of
+        self.state, so checkpoints move freely between this route and the
+        eager one."""
+        cfg = self.config
+        from sat_amd import _C
+        from .ops import hip
+        hip.require()
+        dev = self.params[0].device
+        if getattr(self, 'step_dev', None) is None:
+            self.step_dev = torch.zeros((), dtype=torch.float32, device=dev)
+            self.step_dev.fill_(float(self.step_count - 1))
+        self.step_dev.add_(1.0)
+        # a parameter without grad takes a zero gradient, from one
+        # persistent buffer so that the table stays valid
+        zeros = getattr(self, '_ck_zero', None)
+        if zeros is None:
+            zeros = self._ck_zero = {}
+        grads = []
+        for p in self.params:
+            g = p.grad
+            if g is None:
+                g = zeros.get(p)
+                if g is None:
+                    g = zeros[p] = torch.zeros_like(p)
+            grads.append(g)
+        if self.kind == 'RMSProp':
+            names = ('ms', 'mom', 'mg') if cfg.centered else ('ms', 'mom')
+            kind = _K_RMSC if cfg.centered else _K_RMS
+        elif self.kind == 'Momentum':
+            names = ('mom',)
+            kind = _K_NAG if cfg.use_nesterov else _K_MOM
+        else:
+            names, kind = (), _K_SGD
+        shadows = getattr(self, '_shadows', {})
+        ptrs = tuple(
+            (p.data.data_ptr(), g.data_ptr())
+            + tuple(self.state[p][k].data_ptr() for k in names)
+            + (0,) * (3 - len(names))
+            + (shadows[p].data_ptr() if p in shadows else 0,)
+            for p, g in zip(self.params, grads))
+        if getattr(self, '_ck_ptrs', None) != ptrs:
+            for g, p0 in zip(grads, self.params):
+                # dense storage in either layout: g has p's strides by now,
+                # the slots were allocated like p, and the kernel walks
+                # flat storage order
+                if g.dtype != torch.float32 or not (
+                        g.is_contiguous()
+                        or g.is_contiguous(
+                            memory_format=torch.channels_last)):
+                    raise RuntimeError(
+                        'fused %s needs dense fp32 grads; got '
+                        '%s for a %s param' % (self.kind, g.dtype,
+                                               tuple(p0.shape)))
+            numels = [p.numel() for p in self.params]
+            if max(numels) >= 2 ** 31:
+                raise RuntimeError('fused %s: a tensor of 2^31 or more '
+                                   'elements' % (self.kind,))
+            table = build_chunk_table(numels, MT_CHUNK)
+            # 16-byte route: float4 traffic on p, g and the slots, 8-byte
+            # stores of 4 bf16 to the shadow
+            vec = [int(all(a % 16 == 0 for a in row[:5])
+                       and row[5] % 8 == 0) for row in ptrs]
+            self._ck_ptrs = ptrs
+            self._ck_chunks = torch.tensor(
+                table, dtype=torch.int32).reshape(len(table), 3).to(dev)
+            self._ck_desc = torch.tensor(
+                [list(row) for row in ptrs], dtype=torch.int64).to(dev)
+            self._ck_vec = torch.tensor(vec, dtype=torch.int32).to(dev)
+            self._ck_any_vec = any(vec)
+            if getattr(self, '_ck_partials', None) is None:
+                # one partial of sum g^2 per block of the norm kernel
+                self._ck_partials = torch.zeros(
+                    2048, dtype=torch.float32, device=dev)
+        clip = float(cfg.clip_gradients or 0.0)
+        if clip > 0.0:
+            _C.sq_norm_chunks(self._ck_chunks, self._ck_desc, self._ck_vec,
+                              self._ck_partials)
+        # zero_grads=True: as in the Adam route
+        _C.opt_step_mt(
+            self._ck_chunks, self._ck_desc, self._ck_vec, self._ck_any_vec,
+            self.step_dev, cfg.initial_learning_rate,
+            cfg.learning_rate_decay_factor, cfg.num_steps_per_decay,
+            cfg.momentum, cfg.decay, cfg.epsilon, clip, kind, True,
+            self._ck_partials)
 
     # ---- checkpoint support: optimizer slots are saved like TF's ----
 
