@@ -105,6 +105,11 @@ class Config(object):
         self.use_device_beam = True      # device-resident beam search (one
         #                                  host sync per batch; False = the
         #                                  host-heap reference path)
+        self.use_fused_beam = False      # beam search through the fused,
+        #                                  graph-captured inference engine
+        #                                  (sat_amd/beam.py; GPU bf16, default
+        #                                  architecture, beam <= 8; anything
+        #                                  else keeps the paths above)
         self.use_glds_conv = True        # LDS-staged (glds) implicit-GEMM conv
         #                                  kernels for Cin<=128/Cout>=128 3x3
         #                                  layers (beats MIOpen per

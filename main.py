@@ -6,8 +6,8 @@
     python main.py --phase=test --model_file='./models/xxxxxx.npy' [--beam_size=3]
 
 Same seven flags as reference main.py:15-36 (+ MI355X extras: --device,
---synthetic, --compute_dtype).  Dispatches to train/eval/test on the
-runtime (sat_amd.models.BaseModel), loading checkpoints / pretrained CNNs
+--synthetic, --compute_dtype, --fused_beam, --eval_batch_size).
+Dispatches to train/eval/test on the runtime (sat_amd.models.BaseModel), loading checkpoints / pretrained CNNs
 exactly like reference main.py:49-72.
 """
 
@@ -48,11 +48,17 @@ def build_parser():
                    help='Use synthetic COCO-shaped data (no files/network)')
     p.add_argument('--compute_dtype', default=None,
                    choices=['bf16', 'fp32'])
+    p.add_argument('--fused_beam', action='store_true',
+                   help='Beam search through the fused, graph-captured '
+                        'inference engine (config.use_fused_beam)')
+    p.add_argument('--eval_batch_size', type=int, default=1,
+                   help='Images per beam-search batch in the eval phase '
+                        '(the reference forces 1)')
     return p
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def build_config(args):
+    """Config for the parsed flags."""
     config = Config()
     config.phase = args.phase
     config.train_cnn = args.train_cnn
@@ -62,6 +68,17 @@ def main(argv=None):
         config.synthetic_data = True
     if args.compute_dtype:
         config.compute_dtype = args.compute_dtype
+    if args.fused_beam:
+        config.use_fused_beam = True
+    if args.phase == 'eval':
+        # reference main.py:59 forces eval batch 1 (the default here)
+        config.batch_size = args.eval_batch_size
+    return config
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    config = build_config(args)
 
     torch.manual_seed(config.seed)
 
@@ -75,7 +92,6 @@ def main(argv=None):
         model.train(data)
 
     elif args.phase == 'eval':
-        config.batch_size = 1  # reference main.py:59 forces eval batch 1
         coco, data, vocabulary = prepare_eval_data(config)
         model = BaseModel(config)
         model.load(args.model_file)

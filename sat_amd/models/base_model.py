@@ -264,10 +264,49 @@ class BaseModel(object):
 
         Dispatches to the device-resident scorer (one host sync per
         batch) unless config.use_device_beam is False; the host-heap
-        path below is the semantics reference."""
+        path below is the semantics reference.  With
+        config.use_fused_beam the fused, graph-captured engine
+        (sat_amd/beam.py) takes every batch its GPU form covers."""
+        if getattr(self.config, 'use_fused_beam', False) \
+                and self._fused_beam_mode() == 'hip':
+            return self.beam_search_fused(image_files, vocabulary)
         if getattr(self.config, 'use_device_beam', True):
             return self.beam_search_device(image_files, vocabulary)
         return self.beam_search_host(image_files, vocabulary)
+
+    def _fused_beam_mode(self):
+        """What FusedBeamDecoder offers this model: 'hip' (the GPU
+        engine), 'twin' (its CPU form) or None (not covered)."""
+        if getattr(self, '_fused_beam', None) is None:
+            from ..beam import FusedBeamDecoder
+            self._fused_beam = FusedBeamDecoder(self.model)
+        is_cuda = self.device.type == 'cuda'
+        bf16 = is_cuda and getattr(self.config, 'compute_dtype',
+                                   'bf16') == 'bf16'
+        return self._fused_beam.mode(
+            is_cuda, torch.bfloat16 if bf16 else torch.float32,
+            getattr(self.config, 'beam_size', 3))
+
+    @torch.no_grad()
+    def beam_search_fused(self, image_files, vocabulary):
+        """Beam search through sat_amd.beam.FusedBeamDecoder: per-image
+        work once, the T steps as fused kernels in one captured graph
+        (CPU: the same structure through the op layer's PyTorch twins).
+        Same hypothesis semantics and result structure as
+        beam_search_device, which also serves every configuration the
+        engine does not cover."""
+        if self._fused_beam_mode() is None:
+            return self.beam_search_device(image_files, vocabulary)
+        self.model.eval()
+        images = self._images_to_device(
+            self.image_loader.load_images(image_files))
+        contexts = self.model.compute_contexts(images)
+        try:
+            period = vocabulary.words.index('.')
+        except ValueError:
+            period = -1
+        return self._fused_beam.search(
+            contexts, period, getattr(self.config, 'beam_size', 3))
 
     @torch.no_grad()
     def beam_search_device(self, image_files, vocabulary):

@@ -90,3 +90,30 @@ def masked_softmax_ce(logits, labels, mask):
 
 def dropout(x, rate, training):
     return F.dropout(x, rate, training)
+
+
+def softmax_topk(logits, k, out=None):
+    """The k largest softmax probabilities of each row, ties by ascending
+    index -> (p [R,k] fp32, idx [R,k] int64).  `out=(p, idx)` receives the
+    result in place."""
+    if _use_hip(logits):
+        from . import hip
+        return hip.softmax_topk(logits, k, out)
+    p, idx = F.softmax_topk(logits, k)
+    if out is not None:
+        out[0].copy_(p)
+        out[1].copy_(idx)
+        return out
+    return p, idx
+
+
+def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
+                 table, mem_next, xh_next, exp_next, last_word, parent):
+    """One beam-search bookkeeping step + the next step's inputs
+    (functional.beam_advance documents the contract)."""
+    args = (state_in, state_out, top_p, top_w, period, mem_new, h_new,
+            table, mem_next, xh_next, exp_next, last_word, parent)
+    if _use_hip(table):
+        from . import hip
+        return hip.beam_advance(*args)
+    return F.beam_advance(*args)

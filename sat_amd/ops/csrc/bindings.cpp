@@ -169,6 +169,16 @@ std::vector<at::Tensor> dexp_lstm_bwd_slabs(
     at::Tensor c_prev, at::Tensor dc, at::Tensor dgates_out, double p_fc,
     double p_lstm, int64_t s, int64_t D, int64_t E, double fb);
 
+// beam-search inference (beam.hip, sat_amd/beam.py)
+void softmax_topk(at::Tensor logits, int64_t K, at::Tensor p,
+                  at::Tensor idx);
+void beam_advance(std::vector<at::Tensor> state_in,
+                  std::vector<at::Tensor> state_out, at::Tensor top_p,
+                  at::Tensor top_w, int64_t period, at::Tensor mem_new,
+                  at::Tensor h_new, at::Tensor table, at::Tensor mem_next,
+                  at::Tensor xh_next, at::Tensor exp_next,
+                  at::Tensor last_word, at::Tensor parent);
+
 // The frozen-VGG producers take `emit_pad` (write a 1-px zero-bordered
 // [B,C,H+2,W+2] output for the next 3x3 conv) and an optional caller-
 // supplied `out`; both default to the plain unpadded, freshly allocated
@@ -257,4 +267,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "bf16(sum of split-K slabs * dropout mask)");
     m.def("dexp_lstm_bwd_slabs", &dexp_lstm_bwd_slabs,
           "dexp_lstm_bwd taking d_out_carry as split-K slabs + salt");
+    m.def("softmax_topk", &softmax_topk,
+          "K largest softmax probabilities per row into p / idx; ties by "
+          "ascending index");
+    m.def("beam_advance", &beam_advance,
+          "beam bookkeeping of one step + the next step's LSTM / decode "
+          "input rows in one launch");
 }

@@ -13,6 +13,8 @@ Semantics mirror the TF ops the reference launches:
   * embedding       — tf.nn.embedding_lookup (model.py:273)
   * masked_softmax_ce — tf.nn.sparse_softmax_cross_entropy_with_logits ×
                       mask (model.py:294-297)
+  * softmax_topk / beam_advance — the beam-search inference pair
+                      (sat_amd/beam.py); no reference analog
 """
 
 import torch
@@ -79,3 +81,92 @@ def dropout(x, rate, training):
     if not training or rate <= 0.0:
         return x
     return tF.dropout(x, p=rate, training=True)
+
+
+# ---- beam-search inference (twins of csrc/beam.hip) ----
+
+def softmax_topk(logits, k):
+    """The k largest softmax probabilities of each row -> (p [R,k] fp32,
+    idx [R,k] int64).  Ranked on the logits, descending; equal logits by
+    ascending index (torch.topk promises no order among ties, and bf16
+    logits tie often)."""
+    x = logits.float()
+    v, idx = torch.sort(x, dim=1, descending=True, stable=True)
+    v, idx = v[:, :k], idx[:, :k]
+    mx = v[:, :1]
+    denom = torch.exp(x - mx).sum(dim=1, keepdim=True)
+    return torch.exp(v - mx) / denom, idx
+
+
+def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
+                 table, mem_next, xh_next, exp_next, last_word, parent):
+    """One beam-search bookkeeping step (semantics of
+    BaseModel.beam_search_device between two decode_step calls) plus the
+    next step's inputs.
+
+    state_* = (scores [B,W] fp64, seqs [B,W,T], lens [B,W], c_scores,
+    c_seqs, c_lens); state_out and every tensor after `table` are written
+    in place.  Candidate parent*K + k scores scores[parent] * top_p in
+    fp64; period candidates merge into the completed set (best W of
+    [completed..., candidates...]), the best W others become the live
+    beams (dead slots: score 0).  Every selection is by score descending,
+    then position ascending.  The selected parents' rows of mem_new / h_new
+    go to mem_next and the state columns of xh_next [B*W, D+E+H]; the
+    selected words' embeddings to the E columns of xh_next and (when given)
+    of exp_next [B*W, H+D+E]; the words to last_word, the parents to
+    `parent`."""
+    scores, seqs, lens, c_scores, c_seqs, c_lens = state_in
+    B, W = scores.shape
+    T = seqs.shape[2]
+    K = top_p.shape[1]
+    H, E = mem_new.shape[1], table.shape[1]
+    D = xh_next.shape[1] - E - H
+    dev = scores.device
+    neg = float('-inf')
+
+    cand = (scores.unsqueeze(2)
+            * top_p.double().reshape(B, W, K)).reshape(B, W * K)
+    cand = torch.nan_to_num(cand, nan=0.0)
+    cand_w = top_w.reshape(B, W * K)
+    is_period = cand_w == period
+    par = (torch.arange(W * K, device=dev) // K).reshape(1, -1) \
+        .expand(B, -1)
+    par_len = lens.gather(1, par)
+    step_seq = seqs.gather(1, par.unsqueeze(2).expand(B, W * K, T)) \
+        .scatter(2, par_len.clamp(max=T - 1).unsqueeze(2),
+                 cand_w.unsqueeze(2))
+    step_len = (par_len + 1).clamp(max=T)
+
+    # completed: best W of [completed..., period candidates...]
+    merged_s = torch.cat(
+        [c_scores, torch.where(is_period, cand, torch.zeros_like(cand))],
+        dim=1)
+    keep = torch.sort(merged_s, dim=1, descending=True,
+                      stable=True)[1][:, :W]
+    merged_seq = torch.cat([c_seqs, step_seq], dim=1)
+    merged_len = torch.cat([c_lens, step_len], dim=1)
+    new_c = (merged_s.gather(1, keep),
+             merged_seq.gather(1, keep.unsqueeze(2).expand(B, W, T)),
+             merged_len.gather(1, keep))
+
+    # live: best W non-period candidates
+    part = torch.where(is_period, torch.full_like(cand, neg), cand)
+    sel = torch.sort(part, dim=1, descending=True, stable=True)[1][:, :W]
+    sel_parent = sel // K
+    words = cand_w.gather(1, sel)
+    new_live = (part.gather(1, sel).clamp_min(0.0),
+                step_seq.gather(1, sel.unsqueeze(2).expand(B, W, T)),
+                step_len.gather(1, sel))
+
+    for dst, src in zip(state_out, new_live + new_c):
+        dst.copy_(src)
+    rows = (sel_parent
+            + torch.arange(B, device=dev).unsqueeze(1) * W).reshape(-1)
+    mem_next.copy_(mem_new[rows])
+    xh_next[:, D + E:] = h_new[rows]
+    emb = table[words.reshape(-1).clamp(0, table.shape[0] - 1)]
+    xh_next[:, D:D + E] = emb
+    if exp_next is not None and exp_next.numel() > 0:
+        exp_next[:, H + D:] = emb
+    last_word.copy_(words.reshape(-1))
+    parent.copy_(sel_parent.reshape(parent.shape))

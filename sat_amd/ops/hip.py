@@ -9,6 +9,7 @@ sat_amd/ops/csrc/*.hip, gfx950-only) provides:
   embedding_fwd / embedding_bwd   gather / scatter-add
   ce_fwd / ce_bwd                 fused masked softmax cross-entropy
   grad_sq_norm / adam_step        fused global-norm clip + Adam
+  softmax_topk / beam_advance     beam-search inference (sat_amd/beam.py)
 
 Backward GEMMs (dX = dY·W, dW = dYᵀ·X) go through torch.matmul, i.e.
 hipBLASLt — plain library GEMMs per the MI355X design rules; everything
@@ -213,6 +214,27 @@ class _MaskedCE(torch.autograd.Function):
 
 def masked_softmax_ce(logits, labels, mask):
     return _MaskedCE.apply(logits.contiguous(), labels, mask)
+
+
+# ---- beam-search inference (no autograd; called by sat_amd.beam) ----
+
+def softmax_topk(logits, k, out=None):
+    """logits [R,V] bf16 -> (p [R,k] fp32, idx [R,k] int64), written into
+    `out` when given."""
+    if out is None:
+        R = logits.shape[0]
+        out = (torch.empty(R, k, dtype=torch.float32, device=logits.device),
+               torch.empty(R, k, dtype=torch.int64, device=logits.device))
+    _C.softmax_topk(logits, int(k), out[0], out[1])
+    return out
+
+
+def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
+                 table, mem_next, xh_next, exp_next, last_word, parent):
+    _C.beam_advance(list(state_in), list(state_out), top_p, top_w,
+                    int(period), mem_new, h_new, table, mem_next, xh_next,
+                    exp_next if exp_next is not None else _empty(table.device),
+                    last_word, parent)
 
 
 # ---- fused optimizer (no autograd; called by sat_amd.optim) ----

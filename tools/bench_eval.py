@@ -2,10 +2,11 @@
 """Eval (beam search) throughput: captions/sec at beam=3, batched.
 
     python tools/bench_eval.py [--batch 64] [--batches 5] [--beam 3]
-                               [--host-beam]
+                               [--host-beam | --fused] [--repeats 1]
 
 Measures the device-resident beam path (or the host-heap reference path
-with --host-beam) on the flagship eval model shape: VGG16 frozen,
+with --host-beam, or the fused graph-captured engine with --fused) on the
+flagship eval model shape: VGG16 frozen,
 LSTM-512, vocab 5000, synthetic images.
 """
 import argparse
@@ -23,6 +24,10 @@ def main():
     p.add_argument('--batches', type=int, default=5)
     p.add_argument('--beam', type=int, default=3)
     p.add_argument('--host-beam', action='store_true')
+    p.add_argument('--fused', action='store_true',
+                   help='config.use_fused_beam (sat_amd/beam.py)')
+    p.add_argument('--repeats', type=int, default=1,
+                   help='timed windows of --batches batches each')
     args = p.parse_args()
 
     from config import Config
@@ -35,6 +40,7 @@ def main():
     cfg.synthetic_data = True
     cfg.beam_size = args.beam
     cfg.use_device_beam = not args.host_beam
+    cfg.use_fused_beam = args.fused
     torch.manual_seed(cfg.seed)
 
     vocab = Vocabulary(cfg.vocabulary_size)
@@ -46,16 +52,18 @@ def main():
     m.beam_search(files, vocab)  # warmup
     if torch.cuda.is_available():
         torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.batches):
-        m.beam_search(files, vocab)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    n = args.batch * args.batches
-    print('%s beam=%d batch=%d: %.1f captions/sec (%.1f ms/batch)'
-          % ('host' if args.host_beam else 'device', args.beam,
-             args.batch, n / dt, dt / args.batches * 1000))
+    name = 'fused' if args.fused else 'host' if args.host_beam else 'device'
+    for _ in range(args.repeats):
+        t0 = time.perf_counter()
+        for _ in range(args.batches):
+            m.beam_search(files, vocab)
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        n = args.batch * args.batches
+        print('%s beam=%d batch=%d: %.1f captions/sec (%.1f ms/batch)'
+              % (name, args.beam, args.batch, n / dt,
+                 dt / args.batches * 1000), flush=True)
 
 
 if __name__ == '__main__':
