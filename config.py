@@ -122,6 +122,14 @@ class Config(object):
         #                                  capturable; False = eager PyTorch
         #                                  math with host syncs).  Adam is
         #                                  always fused on the GPU.
+        self.use_adam_chunk_norm = True  # Adam's norm and update over the
+        #                                  chunk table (one partial per block,
+        #                                  fixed-order sum: reproducible);
+        #                                  False = the per-element-search
+        #                                  pair with an atomic norm
+        self.cache_frozen_conv_cast = True  # a frozen conv keeps its bf16
+        #                                  weight and bias across forwards
+        #                                  instead of casting them every step
 
         # Optional JSON overrides from the environment (testing / ops
         # hook): SAT_CONFIG_OVERRIDES='{"batch_size": 2, ...}'

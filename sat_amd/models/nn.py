@@ -208,6 +208,35 @@ class Dense(tnn.Module):
         return y
 
 
+class _WatchedParameter(tnn.Parameter):
+    """A parameter that counts the accesses to its `.data`.
+
+    `p.data` is an alias with a version counter of its own, so a write
+    through it (`p.data.copy_(...)`) leaves `p._version` where it was and
+    a cache keyed on `_version` alone would go stale.  Conv2d keys its
+    cast cache on this count as well and treats every access as a possible
+    write.  Nothing on the training path reads `.data` of a frozen
+    parameter, so the cache is not disturbed there.
+
+    Limits: an alias taken earlier (`d = p.data`) and written to after
+    the cast was cached is not seen, nor is a raw-pointer write by a
+    kernel; and a pickled parameter comes back as a plain Parameter, whose
+    cache then follows `_version` alone.  Code that writes a frozen conv
+    parameter in such a way sets `conv._cast_cache = None`."""
+
+    _data_reads = 0
+
+    @property
+    def data(self):
+        self._data_reads += 1
+        return torch.Tensor.data.__get__(self)
+
+    @data.setter
+    def data(self, value):
+        self._data_reads += 1
+        torch.Tensor.data.__set__(self, value)
+
+
 class Conv2d(tnn.Module):
     """conv2d + bias + optional ReLU (reference nn.py:45-70 defaults:
     3x3, stride 1, SAME padding, ReLU)."""
@@ -221,12 +250,14 @@ class Conv2d(tnn.Module):
         self._nn = nn_policy
         self._glds_conv = getattr(nn_policy.config, 'use_glds_conv',
                                   True)
-        self.weight = tnn.Parameter(
+        self._cast_cache_on = getattr(nn_policy.config,
+                                      'cache_frozen_conv_cast', True)
+        self.weight = _WatchedParameter(
             torch.empty(out_ch, in_ch, kernel_size, kernel_size))
         nn_policy.init_conv_(self.weight)
         nn_policy.register_conv_kernel(self.weight)
         if use_bias:
-            self.bias = tnn.Parameter(torch.zeros(out_ch))
+            self.bias = _WatchedParameter(torch.zeros(out_ch))
         else:
             self.register_parameter('bias', None)
 
@@ -280,9 +311,31 @@ class Conv2d(tnn.Module):
         ok = getattr(self, '_pad_consumer_ok', None)
         return ok is None or ok(M)
 
+    def _cast_operands(self, dtype):
+        """Weight and bias in the compute dtype.  A frozen layer (no grad
+        mode, parameters that do not require grad) casts once and keeps
+        the result until a parameter is written to (`_version`, as for
+        `_w_ohwi`, and the `.data` accesses of _WatchedParameter), moved,
+        or the dtype changes; every other caller gets a fresh cast that
+        stays in the autograd graph."""
+        w, b = self.weight, self.bias
+        frozen = (self._cast_cache_on and not torch.is_grad_enabled()
+                  and not w.requires_grad
+                  and (b is None or not b.requires_grad))
+        if not frozen:
+            return w.to(dtype), (b.to(dtype) if b is not None else None)
+        key = (w._version, getattr(w, '_data_reads', 0),
+               b._version if b is not None else -1,
+               getattr(b, '_data_reads', 0), dtype,
+               w.device, w.data_ptr(), w.stride())
+        cache = getattr(self, '_cast_cache', None)
+        if cache is None or cache[0] != key:
+            cache = (key, w.to(dtype), b.to(dtype) if b is not None else None)
+            self._cast_cache = cache
+        return cache[1], cache[2]
+
     def forward(self, x):
-        w = self.weight.to(x.dtype)
-        b = self.bias.to(x.dtype) if self.bias is not None else None
+        w, b = self._cast_operands(x.dtype)
         k, st = self.kernel_size, self.stride
         # chained-pad handshake: a producing conv or pool may hand over a
         # 1-px zero-bordered output (tagged `_sat_pad`); a 3x3/s1 consumer

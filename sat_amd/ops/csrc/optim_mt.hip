@@ -17,12 +17,13 @@
 // every block of the update kernel sums those <= 2048 partials in a fixed
 // order.  No zero-fill launch, and the step is bitwise reproducible.
 //
-// Slots per kind:  SGD none | Momentum mom | RMSProp ms, mom, (mg)
+// Slots per kind:  SGD none | Momentum mom | RMSProp ms, mom, (mg) | Adam m, v
 #include "common.h"
 
 namespace {
 
-enum { OPT_SGD = 0, OPT_MOM = 1, OPT_NAG = 2, OPT_RMS = 3, OPT_RMSC = 4 };
+enum { OPT_SGD = 0, OPT_MOM = 1, OPT_NAG = 2, OPT_RMS = 3, OPT_RMSC = 4,
+       OPT_ADAM = 5 };
 
 constexpr int MT_BLOCK = 256;
 constexpr int MT_MAX_GRID = 2048;   // 256 CUs x 8 blocks
@@ -31,7 +32,8 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 template <int KIND> struct NSlots {
     static constexpr int value =
-        KIND == OPT_SGD ? 0 : (KIND <= OPT_NAG ? 1 : (KIND == OPT_RMS ? 2 : 3));
+        KIND == OPT_SGD ? 0 : (KIND <= OPT_NAG ? 1 :
+                               (KIND == OPT_RMSC ? 3 : 2));
 };
 
 // sum over the 256 threads of a block in a fixed order; every thread gets it
@@ -73,9 +75,28 @@ __global__ __launch_bounds__(MT_BLOCK) void sq_norm_chunks_kernel(
     if (tid == 0) partials[blockIdx.x] = s;
 }
 
+// Adam reads beta1 from `momentum`, beta2 from `decay`; bc1 / bc2 are its
+// bias corrections 1 - beta^step
 struct OptHyper {
-    float lr, scale, momentum, decay, eps;
+    float lr, scale, momentum, decay, eps, bc1, bc2;
 };
+
+// m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g g with the first product
+// of each sum fused, as adam_mt_kernel has them; g is already scaled.
+// adam_mt_kernel (kernels.hip) leaves that choice to the compiler's
+// contraction, so the bit equality of the two routes that
+// tests/test_adam_chunk_norm_gpu.py asserts holds for the compiler that
+// fuses it this way; should another one not, spell the same fmaf calls out
+// there.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m,
+                                            float& v, const OptHyper& h) {
+#pragma clang fp contract(off)
+    const float mi = fmaf(h.momentum, m, (1.f - h.momentum) * g);
+    const float vi = fmaf(h.decay, v, (1.f - h.decay) * g * g);
+    m = mi;
+    v = vi;
+    p -= h.lr * (mi / h.bc1) / (sqrtf(vi / h.bc2) + h.eps);
+}
 
 // one element; g is the raw gradient, s[] the slots of KIND
 template <int KIND>
@@ -90,6 +111,11 @@ __device__ __forceinline__ void opt_update(float& p, float g, float* s,
     } else if (KIND == OPT_NAG) {
         s[0] = h.momentum * s[0] + g;
         p -= h.lr * (g + h.momentum * s[0]);
+    } else if (KIND == OPT_ADAM) {
+        // the expressions of adam_mt_kernel (kernels.hip) with the FMAs
+        // it compiles to spelled out (contraction is off in adam_update):
+        // left to the compiler, this kernel fused the other product
+        adam_update(p, g, s[0], s[1], h);
     } else {
         // TF RMSProp: epsilon inside the sqrt, var -= mom
         s[0] = h.decay * s[0] + (1.f - h.decay) * g * g;
@@ -126,6 +152,11 @@ __global__ __launch_bounds__(MT_BLOCK, 8) void opt_mt_kernel(
     h.lr = lr0;
     if (decay_factor < 1.f)
         h.lr = lr0 * powf(decay_factor, floorf(step / steps_per_decay));
+    h.bc1 = h.bc2 = 1.f;
+    if (KIND == OPT_ADAM) {
+        h.bc1 = 1.f - powf(momentum, step);
+        h.bc2 = 1.f - powf(decay, step);
+    }
     h.scale = 1.f;
     if (clip > 0.f) {
         // the same fixed-order sum in every block: one scale for all
@@ -242,9 +273,10 @@ void sq_norm_chunks(at::Tensor chunks, at::Tensor ptrs, at::Tensor vec,
 }
 
 // kind: 0 SGD, 1 Momentum, 2 Momentum-Nesterov, 3 RMSProp, 4 RMSProp
-// centered.  any_vec: some vec[t] is set (host-known; reading it back here
-// would sync inside a graph capture).  With clip > 0, partials holds what
-// sq_norm_chunks wrote for the same tables.
+// centered, 5 Adam (momentum = beta1, decay = beta2).  any_vec: some
+// vec[t] is set (host-known; reading it back here would sync inside a
+// graph capture).  With clip > 0, partials holds what sq_norm_chunks wrote
+// for the same tables.
 void opt_step_mt(at::Tensor chunks, at::Tensor ptrs, at::Tensor vec,
                  bool any_vec, at::Tensor step_dev, double lr0,
                  double decay_factor, double steps_per_decay,
@@ -252,7 +284,7 @@ void opt_step_mt(at::Tensor chunks, at::Tensor ptrs, at::Tensor vec,
                  int64_t kind, bool zero_grads, at::Tensor partials) {
     Tables T = check_tables(chunks, ptrs, vec, partials);
     CHECK_GPU(step_dev); CHECK_F32(step_dev);
-    TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_RMSC, "unknown kind ", kind);
+    TORCH_CHECK(kind >= OPT_SGD && kind <= OPT_ADAM, "unknown kind ", kind);
     if (T.n_chunks == 0) return;
     hipStream_t s = at::cuda::getCurrentCUDAStream();
 #define OPT_LAUNCH(K, V) \
@@ -271,6 +303,7 @@ void opt_step_mt(at::Tensor chunks, at::Tensor ptrs, at::Tensor vec,
         OPT_KIND(OPT_NAG);
         OPT_KIND(OPT_RMS);
         OPT_KIND(OPT_RMSC);
+        OPT_KIND(OPT_ADAM);
     }
 #undef OPT_KIND
 #undef OPT_LAUNCH

@@ -12,12 +12,15 @@ launch each over all ~14M decoder params instead of per-tensor eager ops,
 with the step counter, the LR staircase and the clip scale on the device,
 so the step has no host sync and is hipGraph-capturable:
 
-  * Adam: sq_norm_mt + adam_step_mt (sat_amd/ops/csrc/kernels.hip), over
-    the concatenation of all tensors;
-  * RMSProp, Momentum, SGD: sq_norm_chunks + opt_step_mt
+  * every kind: sq_norm_chunks + opt_step_mt
     (sat_amd/ops/csrc/optim_mt.hip), over a host-built table of chunks of
-    MT_CHUNK elements that never cross a tensor.  `use_fused_optimizer =
-    False` sends these three down the eager path instead.
+    MT_CHUNK elements that never cross a tensor; the norm is one partial
+    per block summed in a fixed order, so a step is bitwise reproducible.
+    `use_fused_optimizer = False` sends RMSProp, Momentum and SGD down the
+    eager path instead; Adam is always fused on the GPU.
+  * `use_adam_chunk_norm = False` keeps Adam on its earlier pair
+    sq_norm_mt + adam_step_mt (sat_amd/ops/csrc/kernels.hip): one search
+    per element over the concatenation of all tensors, atomics in the norm.
 
 The eager path (PyTorch math, one host sync per tensor for the norm) serves
 the CPU.
@@ -34,7 +37,7 @@ MT_CHUNK = 1024
 
 FUSED_KINDS = ('Adam', 'RMSProp', 'Momentum', 'SGD')
 # kernel codes of optim_mt.hip
-_K_SGD, _K_MOM, _K_NAG, _K_RMS, _K_RMSC = range(5)
+_K_SGD, _K_MOM, _K_NAG, _K_RMS, _K_RMSC, _K_ADAM = range(6)
 
 
 def build_chunk_table(numels, chunk=MT_CHUNK):
@@ -133,8 +136,11 @@ class Optimizer(object):
                     p.grad = torch.empty_like(p, dtype=g.dtype).copy_(g)
         if fused and not use_hip:
             return self._step_chunks()
-        grads = [p.grad if p.grad is not None else torch.zeros_like(p)
-                 for p in self.params]
+        if use_hip:
+            grads = self._dense_grads()
+        else:
+            grads = [p.grad if p.grad is not None else torch.zeros_like(p)
+                     for p in self.params]
 
         if use_hip:
             from sat_amd import _C
@@ -186,6 +192,13 @@ class Optimizer(object):
                             'fused Adam needs dense fp32 grads; got '
                             '%s for a %s param' % (g.dtype,
                                                    tuple(p0.shape)))
+            if getattr(cfg, 'use_adam_chunk_norm', True):
+                # the norm as one partial per block over the chunk table,
+                # summed in a fixed order by every block of the update
+                # (the _mt_* tables above are kept for the earlier route
+                # below and for the tests that read them)
+                return self._launch_chunks(
+                    grads, ('m', 'v'), _K_ADAM, cfg.beta1, cfg.beta2)
             gsq = _C.sq_norm_mt(self._mt_desc, self._mt_cum,
                                 len(self.params), self._mt_total)
             # zero_grads=True: the update kernel clears p.grad in the
@@ -241,23 +254,9 @@ class Optimizer(object):
             p.data.add_(upd.to(p.dtype), alpha=-lr)
         self.sync_shadows()
 
-    def _step_chunks(self):
-        """RMSProp / Momentum / SGD through optim_mt.hip: two launches (one
-        without clipping) and the counter's add_, no host sync, nothing
-        allocated after the first call.  The slots are the tensors of
-        self.state, so checkpoints move freely between this route and the
-        eager one."""
-        cfg = self.config
-        from sat_amd import _C
-        from .ops import hip
-        hip.require()
-        dev = self.params[0].device
-        if getattr(self, 'step_dev', None) is None:
-            self.step_dev = torch.zeros((), dtype=torch.float32, device=dev)
-            self.step_dev.fill_(float(self.step_count - 1))
-        self.step_dev.add_(1.0)
-        # a parameter without grad takes a zero gradient, from one
-        # persistent buffer so that the table stays valid
+    def _dense_grads(self):
+        """p.grad per parameter; one without grad takes a zero gradient
+        from a persistent buffer, so that the pointer tables stay valid"""
         zeros = getattr(self, '_ck_zero', None)
         if zeros is None:
             zeros = self._ck_zero = {}
@@ -269,6 +268,22 @@ class Optimizer(object):
                 if g is None:
                     g = zeros[p] = torch.zeros_like(p)
             grads.append(g)
+        return grads
+
+    def _step_chunks(self):
+        """RMSProp / Momentum / SGD through optim_mt.hip: two launches (one
+        without clipping) and the counter's add_, no host sync, nothing
+        allocated after the first call.  The slots are the tensors of
+        self.state, so checkpoints move freely between this route and the
+        eager one."""
+        cfg = self.config
+        from .ops import hip
+        hip.require()
+        dev = self.params[0].device
+        if getattr(self, 'step_dev', None) is None:
+            self.step_dev = torch.zeros((), dtype=torch.float32, device=dev)
+            self.step_dev.fill_(float(self.step_count - 1))
+        self.step_dev.add_(1.0)
         if self.kind == 'RMSProp':
             names = ('ms', 'mom', 'mg') if cfg.centered else ('ms', 'mom')
             kind = _K_RMSC if cfg.centered else _K_RMS
@@ -277,6 +292,16 @@ class Optimizer(object):
             kind = _K_NAG if cfg.use_nesterov else _K_MOM
         else:
             names, kind = (), _K_SGD
+        self._launch_chunks(self._dense_grads(), names, kind,
+                            cfg.momentum, cfg.decay)
+
+    def _launch_chunks(self, grads, names, kind, momentum, decay):
+        """sq_norm_chunks (with clipping) + opt_step_mt over the chunk
+        table of `grads` and the state slots `names`; step_dev is already
+        advanced.  Adam passes beta1 / beta2 as momentum / decay."""
+        cfg = self.config
+        from sat_amd import _C
+        dev = self.params[0].device
         shadows = getattr(self, '_shadows', {})
         ptrs = tuple(
             (p.data.data_ptr(), g.data_ptr())
@@ -321,12 +346,14 @@ class Optimizer(object):
         if clip > 0.0:
             _C.sq_norm_chunks(self._ck_chunks, self._ck_desc, self._ck_vec,
                               self._ck_partials)
-        # zero_grads=True: as in the Adam route
+        # zero_grads=True: the update kernel clears p.grad in the same
+        # pass, so the engine skips its per-tensor fill launches and
+        # autograd accumulates into stable addresses
         _C.opt_step_mt(
             self._ck_chunks, self._ck_desc, self._ck_vec, self._ck_any_vec,
             self.step_dev, cfg.initial_learning_rate,
             cfg.learning_rate_decay_factor, cfg.num_steps_per_decay,
-            cfg.momentum, cfg.decay, cfg.epsilon, clip, kind, True,
+            momentum, decay, cfg.epsilon, clip, kind, True,
             self._ck_partials)
 
     # ---- checkpoint support: optimizer slots are saved like TF's ----
