@@ -131,6 +131,18 @@ class Config(object):
         #                                  weight and bias across forwards
         #                                  instead of casting them every step
 
+        # input pipeline (sat_amd/data/pipeline.py); the defaults keep the
+        # synchronous load-then-step loop
+        self.num_loader_threads = 0      # > 0: that many threads (at most
+        #                                  16) decode the coming batches'
+        #                                  files while the GPU works
+        self.prefetch_batches = 2        # how many batches they run ahead
+        self.device_image_prep = False   # resize, mean and cast on the
+        #                                  device from the decoded uint8
+        #                                  images (same bits as the host
+        #                                  path; real files, per-channel
+        #                                  mean only)
+
         # Optional JSON overrides from the environment (testing / ops
         # hook): SAT_CONFIG_OVERRIDES='{"batch_size": 2, ...}'
         import json as _json

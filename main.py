@@ -6,7 +6,8 @@
     python main.py --phase=test --model_file='./models/xxxxxx.npy' [--beam_size=3]
 
 Same seven flags as reference main.py:15-36 (+ MI355X extras: --device,
---synthetic, --compute_dtype, --fused_beam, --eval_batch_size).
+--synthetic, --compute_dtype, --fused_beam, --eval_batch_size,
+--loader_threads, --device_image_prep).
 Dispatches to train/eval/test on the runtime (sat_amd.models.BaseModel), loading checkpoints / pretrained CNNs
 exactly like reference main.py:49-72.
 """
@@ -54,6 +55,13 @@ def build_parser():
     p.add_argument('--eval_batch_size', type=int, default=1,
                    help='Images per beam-search batch in the eval phase '
                         '(the reference forces 1)')
+    p.add_argument('--loader_threads', type=int, default=0,
+                   help='Decode the coming batches\' image files on this '
+                        'many threads (config.num_loader_threads; 0 = '
+                        'load each batch when it is needed)')
+    p.add_argument('--device_image_prep', action='store_true',
+                   help='Resize and normalise images on the device '
+                        '(config.device_image_prep)')
     return p
 
 
@@ -70,6 +78,10 @@ def build_config(args):
         config.compute_dtype = args.compute_dtype
     if args.fused_beam:
         config.use_fused_beam = True
+    if args.loader_threads:
+        config.num_loader_threads = args.loader_threads
+    if args.device_image_prep:
+        config.device_image_prep = True
     if args.phase == 'eval':
         # reference main.py:59 forces eval batch 1 (the default here)
         config.batch_size = args.eval_batch_size

@@ -62,6 +62,8 @@ class BaseModel(object):
         self.model = CaptionGenerator(config).to(self.device)
         self.global_step = 0
         self._engine = None
+        self._prep = None               # ImagePrep, made on first use
+        self._staged = None             # (files, images) loaded ahead
 
         self.is_train = getattr(config, 'phase', 'train') == 'train'
         self.optimizer = Optimizer(
@@ -101,6 +103,67 @@ class BaseModel(object):
         t = t.permute(0, 3, 1, 2).contiguous()
         return t.to(self.device, non_blocking=True)
 
+    # ---- input pipeline (sat_amd/data/pipeline.py; off by default) ----
+
+    def _image_prep(self):
+        """The ImagePrep behind config.device_image_prep, or None: it
+        needs decoded uint8 images (not the synthetic loader) and a
+        per-channel mean."""
+        if not getattr(self.config, 'device_image_prep', False) \
+                or type(self.image_loader) is not ImageLoader \
+                or np.shape(self.image_loader.mean) != (3,):
+            return None
+        if self._prep is None:
+            from ..data.pipeline import ImagePrep
+            bf16 = self.device.type == 'cuda' and getattr(
+                self.config, 'compute_dtype', 'bf16') == 'bf16'
+            self._prep = ImagePrep(
+                self.image_loader.mean, self.image_loader.image_shape,
+                self.device, torch.bfloat16 if bf16 else torch.float32)
+        return self._prep
+
+    def _load_batch(self, image_files):
+        """Files -> the [N,3,H,W] image tensor on the device: what
+        `_batches` loaded ahead for exactly this batch, else loaded here,
+        through ImagePrep with config.device_image_prep."""
+        staged, self._staged = self._staged, None
+        if staged is not None and staged[0] is image_files:
+            images = staged[1]
+        elif self._image_prep() is not None:
+            from ..data.pipeline import decode_u8
+            images = self._image_prep()([decode_u8(f) for f in image_files])
+        else:
+            images = self.image_loader.load_images(image_files)
+        if isinstance(images, np.ndarray):
+            images = self._images_to_device(images)
+        if not images.is_cuda:
+            # the CPU encoder runs in the layout it is handed, and its
+            # sums differ in the last bits between layouts: keep NCHW
+            images = images.contiguous()
+        return images
+
+    def _batches(self, data):
+        """One epoch of `data.next_batch()` results.  With
+        config.num_loader_threads > 0 a BatchPrefetcher loads the images
+        of the coming batches on worker threads, and `_load_batch` of a
+        yielded batch's files returns them."""
+        threads = getattr(self.config, 'num_loader_threads', 0)
+        if threads <= 0:
+            for _ in range(data.num_batches):
+                yield data.next_batch()
+            return
+        from ..data.pipeline import BatchPrefetcher
+        prefetcher = BatchPrefetcher(
+            data, self.image_loader, self._image_prep(), threads,
+            getattr(self.config, 'prefetch_batches', 2))
+        try:
+            for batch, images in prefetcher:
+                self._staged = (batch[0] if data.is_train else batch,
+                                images)
+                yield batch
+        finally:
+            prefetcher.close()
+
     def train_step(self, images, sentences, masks):
         """One fwd+bwd+optimizer step on device tensors. Returns loss dict.
 
@@ -131,11 +194,10 @@ class BaseModel(object):
         writer = SummaryWriter(config.summary_dir) if self.is_chief else None
 
         for _ in tqdm(range(config.num_epochs), desc='epoch'):
-            for _ in tqdm(range(train_data.num_batches), desc='batch',
-                          leave=False):
-                image_files, sentences, masks = train_data.next_batch()
-                images = self._images_to_device(
-                    self.image_loader.load_images(image_files))
+            for image_files, sentences, masks in tqdm(
+                    self._batches(train_data), total=train_data.num_batches,
+                    desc='batch', leave=False):
+                images = self._load_batch(image_files)
                 sentences = torch.as_tensor(
                     sentences, dtype=torch.int64).to(self.device)
                 masks = torch.as_tensor(
@@ -178,8 +240,9 @@ class BaseModel(object):
         os.makedirs(config.eval_result_dir, exist_ok=True)
         results = []
         idx = 0
-        for k in tqdm(range(eval_data.num_batches), desc='batch'):
-            batch = eval_data.next_batch()
+        for k, batch in enumerate(tqdm(
+                self._batches(eval_data), total=eval_data.num_batches,
+                desc='batch')):
             caption_data = self.beam_search(batch, vocabulary)
 
             fake_cnt = 0 if k < eval_data.num_batches - 1 \
@@ -209,8 +272,9 @@ class BaseModel(object):
         config = self.config
         os.makedirs(config.test_result_dir, exist_ok=True)
         captions, scores = [], []
-        for k in tqdm(range(test_data.num_batches), desc='path'):
-            batch = test_data.next_batch()
+        for k, batch in enumerate(tqdm(
+                self._batches(test_data), total=test_data.num_batches,
+                desc='path')):
             caption_data = self.beam_search(batch, vocabulary)
             fake_cnt = 0 if k < test_data.num_batches - 1 \
                 else test_data.fake_count
@@ -298,8 +362,7 @@ class BaseModel(object):
         if self._fused_beam_mode() is None:
             return self.beam_search_device(image_files, vocabulary)
         self.model.eval()
-        images = self._images_to_device(
-            self.image_loader.load_images(image_files))
+        images = self._load_batch(image_files)
         contexts = self.model.compute_contexts(images)
         try:
             period = vocabulary.words.index('.')
@@ -325,8 +388,7 @@ class BaseModel(object):
         T = config.max_caption_length
         dev = self.device
 
-        images = self._images_to_device(
-            self.image_loader.load_images(image_files))
+        images = self._load_batch(image_files)
         contexts, init_memory, init_output = self.model.encode(images)
         H = init_memory.shape[1]
 
@@ -435,8 +497,7 @@ class BaseModel(object):
         beam_size = getattr(config, 'beam_size', 3)
         B = len(image_files)
 
-        images = self._images_to_device(
-            self.image_loader.load_images(image_files))
+        images = self._load_batch(image_files)
         contexts, initial_memory, initial_output = self.model.encode(images)
 
         partial = []

@@ -107,6 +107,21 @@ def softmax_topk(logits, k, out=None):
     return p, idx
 
 
+def resize_normalize_u8(packed, desc, tables, mean, out_h, out_w,
+                        dtype=torch.float32):
+    """Packed uint8 HWC images of any sizes -> [N,3,out_h,out_w]
+    channels_last in `dtype` (bf16 or fp32): Pillow's 8-bit bilinear
+    resize bit for bit, minus the per-channel mean
+    (functional.resize_normalize_u8 documents the tables)."""
+    if packed.is_cuda:
+        from . import hip
+        hip.require()
+        return hip.resize_normalize_u8(packed, desc, tables, mean, out_h,
+                                       out_w, dtype)
+    return F.resize_normalize_u8(packed, desc, tables, mean, out_h, out_w,
+                                 dtype)
+
+
 def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
                  table, mem_next, xh_next, exp_next, last_word, parent):
     """One beam-search bookkeeping step + the next step's inputs

@@ -178,6 +178,9 @@ void beam_advance(std::vector<at::Tensor> state_in,
                   at::Tensor h_new, at::Tensor table, at::Tensor mem_next,
                   at::Tensor xh_next, at::Tensor exp_next,
                   at::Tensor last_word, at::Tensor parent);
+at::Tensor resize_normalize_u8(at::Tensor packed, at::Tensor desc,
+                               at::Tensor tables, at::Tensor mean,
+                               int64_t OH, int64_t OW, bool bf16_out);
 
 // The frozen-VGG producers take `emit_pad` (write a 1-px zero-bordered
 // [B,C,H+2,W+2] output for the next 3x3 conv) and an optional caller-
@@ -273,4 +276,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("beam_advance", &beam_advance,
           "beam bookkeeping of one step + the next step's LSTM / decode "
           "input rows in one launch");
+    m.def("resize_normalize_u8", &resize_normalize_u8,
+          "packed uint8 HWC images -> [N,3,OH,OW] channels_last: Pillow's "
+          "8-bit bilinear resize, minus the mean, as bf16 or fp32");
 }

@@ -15,6 +15,8 @@ Semantics mirror the TF ops the reference launches:
                       mask (model.py:294-297)
   * softmax_topk / beam_advance — the beam-search inference pair
                       (sat_amd/beam.py); no reference analog
+  * resize_normalize_u8 — Pillow's 8-bit bilinear resize in integers, mean
+                      subtraction and the cast (sat_amd/data/pipeline.py)
 """
 
 import torch
@@ -170,3 +172,48 @@ def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
         exp_next[:, H + D:] = emb
     last_word.copy_(words.reshape(-1))
     parent.copy_(sel_parent.reshape(parent.shape))
+
+
+def _resample_u8(src, table, out_size, ksize, dim):
+    """One pass of Pillow's 8-bit resample along `dim` of src [H,W,3]
+    uint8.  `table` is an axis table of ImagePrep: first source index and
+    tap count per output, then out_size x ksize Q22 coefficients (zero
+    past the tap count)."""
+    first = table[:out_size].long()
+    coef = table[2 * out_size:].reshape(out_size, ksize)
+    last = src.shape[dim] - 1
+    shape = [1, 1, 1]
+    shape[dim] = out_size
+    acc = None
+    for k in range(ksize):
+        px = src.index_select(dim, (first + k).clamp(max=last))
+        term = px.to(torch.int32) * coef[:, k].reshape(shape)
+        acc = term if acc is None else acc + term
+    return ((acc + (1 << 21)) >> 22).clamp(0, 255).to(torch.uint8)
+
+
+def resize_normalize_u8(packed, desc, tables, mean, out_h, out_w,
+                        dtype=torch.float32):
+    """N packed uint8 HWC images -> [N,3,out_h,out_w] channels_last:
+    Pillow's resize(..., BILINEAR) bit for bit (horizontal pass, then
+    vertical, each rounded to 8 bits), then float(u8) - mean[c] in fp32,
+    then the cast to `dtype`.
+
+    packed: 1-D uint8; desc: [N,8] int64 rows (byte offset, H, W,
+    horizontal table offset, its taps, vertical table offset, its taps,
+    0); tables: 1-D int32 holding the axis tables (ImagePrep builds
+    them); mean: [3] fp32."""
+    N = desc.shape[0]
+    out = torch.empty((N, 3, out_h, out_w), dtype=dtype,
+                      device=packed.device,
+                      memory_format=torch.channels_last)
+    nhwc = out.permute(0, 2, 3, 1)
+    mean = mean.to(torch.float32)
+    for n, (off, H, W, ht, hk, vt, vk, _) in enumerate(desc.tolist()):
+        src = packed[off:off + H * W * 3].reshape(H, W, 3)
+        htab = tables[ht:ht + out_w * (2 + hk)]
+        vtab = tables[vt:vt + out_h * (2 + vk)]
+        px = _resample_u8(src, htab, out_w, hk, 1)
+        px = _resample_u8(px, vtab, out_h, vk, 0)
+        nhwc[n] = (px.to(torch.float32) - mean).to(dtype)
+    return out

@@ -10,6 +10,8 @@ sat_amd/ops/csrc/*.hip, gfx950-only) provides:
   ce_fwd / ce_bwd                 fused masked softmax cross-entropy
   grad_sq_norm / adam_step        fused global-norm clip + Adam
   softmax_topk / beam_advance     beam-search inference (sat_amd/beam.py)
+  resize_normalize_u8             Pillow-exact resize + mean + cast of packed
+                                  uint8 images (sat_amd/data/pipeline.py)
 
 Backward GEMMs (dX = dY·W, dW = dYᵀ·X) go through torch.matmul, i.e.
 hipBLASLt — plain library GEMMs per the MI355X design rules; everything
@@ -235,6 +237,14 @@ def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
                     int(period), mem_new, h_new, table, mem_next, xh_next,
                     exp_next if exp_next is not None else _empty(table.device),
                     last_word, parent)
+
+
+# ---- input pipeline (no autograd; called by sat_amd.data.pipeline) ----
+
+def resize_normalize_u8(packed, desc, tables, mean, out_h, out_w, dtype):
+    """-> [N,3,out_h,out_w] channels_last, bf16 or fp32."""
+    return _C.resize_normalize_u8(packed, desc, tables, mean, int(out_h),
+                                  int(out_w), dtype == torch.bfloat16)
 
 
 # ---- fused optimizer (no autograd; called by sat_amd.optim) ----

@@ -36,6 +36,7 @@ setup(
                 os.path.join(CSRC, 'gemm8p.hip'),
                 os.path.join(CSRC, 'optim_mt.hip'),
                 os.path.join(CSRC, 'beam.hip'),
+                os.path.join(CSRC, 'image_prep.hip'),
             ],
             extra_compile_args={
                 'cxx': ['-O3', '-std=c++17'],
