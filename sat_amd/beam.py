@@ -17,8 +17,9 @@ What makes the loop small (default architecture, 2-layer attend MLP):
 
 Per step, GPU: gates GEMM + gate math + expand (`dense_lstm_expand_fwd`
 where B·W <= 128, else `dense_fwd` + `lstm_pointwise_fwd` + `expand_fuse`),
-decode fc_1, decode fc_2, `softmax_topk`, `beam_advance` — all at drop
-rate 0.  `beam_advance` writes the next step's state and input rows into
+decode fc_1, decode fc_2 (or the one dec_fc), `softmax_topk`,
+`beam_advance` — all at drop rate 0.  `beam_advance` writes the next
+step's state and input rows into
 the other half of a double buffer.  The T steps are captured once per
 (B, W, T) on one stream as one linear chain and replayed; the loop holds no
 host copy and no synchronisation, its state buffers are owned by the
@@ -26,8 +27,22 @@ engine, and the temporaries the existing GEMM entry points allocate come
 from the graph's private pool.  At most MAX_GRAPHS shapes are captured;
 further shapes run the same launches eagerly.
 
+With the 1-layer attention (num_attend_layers == 1) the logits are
+att_fc_a(ctx)[b,l] + att_fc_b(h)[n,l]: the second term differs per
+location, the softmax follows the LSTM state and nothing can be hoisted
+but the first term, l1 [B,L] fp32, computed once per batch.  Each step
+then starts with `beam_attend`, one more launch on the same linear chain
+(7 instead of 6): it reads h from the step's LSTM-input rows, reads each
+image's [L,D] context block once for all its W beams and writes the pooled
+context into `pool` and the context columns of those rows.  The contexts
+and l1 are copied into engine-owned buffers so a captured graph keeps valid
+addresses.  num_decode_layers == 1 is one `dense_fwd` on dec_fc instead
+of two.
+
 On the CPU the same structure runs through the op layer's PyTorch twins
-(hoisted attention, stable top-k, the beam_advance twin), without a graph.
+(hoisted or in-loop attention, stable top-k, the beam_advance twin),
+without a graph.  mode() offers the CPU form for the 2-layer attention
+only; search(mode='twin') runs the in-loop form there as well.
 
 Beam semantics are those of BaseModel.beam_search_device: beam_size + 1
 expansion, '.'-termination, probability-product scores in fp64, completed
@@ -41,14 +56,23 @@ from .ops import functional as F  # noqa: N812
 from .utils.topn import CaptionData
 
 MAX_BEAM = 8
+MAX_CTX = 1024              # locations: attention_tail and beam_attend
+MAX_ATTEND_UNITS = 2048     # LSTM units beam_attend stages in LDS
 
 
 class _Buffers(object):
     """Static per-(B, W, T) state: everything the loop reads or writes."""
 
-    def __init__(self, B, W, T, K, H, D, E, dtype, dev):
+    def __init__(self, B, W, T, K, H, D, E, dtype, dev, L=0, alpha=False):
+        """L > 0: the in-loop attention's inputs (contexts, l1) and, for
+        a trace, its alpha."""
         N = B * W
         z = dict(device=dev)
+        if L:
+            self.ctx = torch.zeros(B, L, D, dtype=dtype, **z)
+            self.l1 = torch.zeros(B, L, dtype=torch.float32, **z)
+        self.alpha = torch.zeros(N, L, dtype=torch.float32, **z) \
+            if L and alpha else None
         self.xh = [torch.zeros(N, D + E + H, dtype=dtype, **z)
                    for _ in range(2)]
         self.mem = [torch.zeros(N, H, dtype=dtype, **z) for _ in range(2)]
@@ -76,6 +100,9 @@ class FusedBeamDecoder(object):
         self.model = model                  # CaptionGenerator
         self.dec = model.decoder
         self.cfg = model.config
+        # 1-layer attention runs inside the loop, 1-layer decode is one GEMM
+        self.inloop = self.cfg.num_attend_layers == 1
+        self.dec1 = self.cfg.num_decode_layers == 1
         self._w = None                      # cached compute-dtype weights
         self._w_key = None
         self._bufs = {}                     # (B,W,T) -> _Buffers (graphed)
@@ -91,22 +118,30 @@ class FusedBeamDecoder(object):
         back to beam_search_device)."""
         cfg = self.cfg
         if not (1 <= beam_size <= MAX_BEAM
-                and cfg.num_attend_layers == 2
-                and cfg.num_decode_layers == 2
+                and cfg.num_attend_layers in (1, 2)
+                and cfg.num_decode_layers in (1, 2)
                 and cfg.vocabulary_size >= beam_size + 1):
             return None
         if not is_cuda:
+            # the in-loop form is reachable on the CPU through
+            # search(mode='twin') only
+            if self.inloop:
+                return None
             return 'twin' if dtype == torch.float32 else None
         ok = (dtype == torch.bfloat16
               and getattr(cfg, 'use_hip_kernels', True)
-              # the shape contracts of CaptionGenerator._use_bptt
-              and cfg.dim_attend_layer % 512 == 0
-              and cfg.dim_attend_layer <= 2048
               and self.model.dim_ctx % 8 == 0
               and cfg.dim_embedding % 8 == 0
               and cfg.num_lstm_units % 8 == 0
-              and cfg.dim_decode_layer % 8 == 0
-              and self.model.num_ctx <= 1024)
+              and self.model.num_ctx <= MAX_CTX)
+        if self.inloop:
+            ok = ok and cfg.num_lstm_units <= MAX_ATTEND_UNITS
+        else:
+            # the shape contracts of CaptionGenerator._use_bptt
+            ok = (ok and cfg.dim_attend_layer % 512 == 0
+                  and cfg.dim_attend_layer <= 2048)
+        if not self.dec1:
+            ok = ok and cfg.dim_decode_layer % 8 == 0
         if not ok:
             return None
         from .ops import hip
@@ -117,11 +152,17 @@ class FusedBeamDecoder(object):
 
     def _params(self):
         d = self.dec
-        named = [('emb', d.embedding), ('wl', d.lstm_w), ('bl', d.lstm_b),
-                 ('w1a', d.att_fc_1a.weight), ('b1a', d.att_fc_1a.bias),
-                 ('v', d.att_fc_2.weight),
-                 ('wd1', d.dec_fc_1.weight), ('bd1', d.dec_fc_1.bias),
-                 ('wd2', d.dec_fc_2.weight), ('bd2', d.dec_fc_2.bias)]
+        named = [('emb', d.embedding), ('wl', d.lstm_w), ('bl', d.lstm_b)]
+        if self.inloop:
+            named += [('wa', d.att_fc_a.weight), ('wb', d.att_fc_b.weight)]
+        else:
+            named += [('w1a', d.att_fc_1a.weight),
+                      ('b1a', d.att_fc_1a.bias), ('v', d.att_fc_2.weight)]
+        if self.dec1:
+            named += [('wd', d.dec_fc.weight), ('bd', d.dec_fc.bias)]
+        else:
+            named += [('wd1', d.dec_fc_1.weight), ('bd1', d.dec_fc_1.bias),
+                      ('wd2', d.dec_fc_2.weight), ('bd2', d.dec_fc_2.bias)]
         if self.cfg.num_initalize_layers == 1:
             init = [('a', d.init_fc_a), ('b', d.init_fc_b)]
         else:
@@ -165,33 +206,43 @@ class FusedBeamDecoder(object):
                 ops.dense(tb, w['wib2'], w['bib2'], None))
 
     def _per_image(self, w, contexts):
-        """-> (memory0, output0, pooled context), each on B rows."""
+        """-> (memory0, output0, attention constant), each on B rows:
+        the pooled context [B,D], or for the in-loop attention l1 [B,L]
+        fp32, the state-independent term of its logits."""
         B, L, D = contexts.shape
         mean = contexts.float().mean(dim=1).to(contexts.dtype)
         mem0, out0 = self._initial_state(w, mean)
-        t1 = ops.dense(contexts.reshape(B * L, D), w['w1a'], w['b1a'],
-                       'tanh')
-        t2 = torch.zeros(B, t1.shape[1], dtype=t1.dtype,
-                         device=t1.device)
         if self._seed is None or self._seed.device != contexts.device:
             self._seed = torch.zeros((), dtype=torch.int64,
                                      device=contexts.device)
             self._empty = torch.empty(0, dtype=contexts.dtype,
                                       device=contexts.device)
+        if self.inloop:
+            l1 = contexts.float().matmul(w['wa'].float().reshape(-1))
+            return mem0, out0, l1
+        t1 = ops.dense(contexts.reshape(B * L, D), w['w1a'], w['b1a'],
+                       'tanh')
+        t2 = torch.zeros(B, t1.shape[1], dtype=t1.dtype,
+                         device=t1.device)
         _alpha, pooled = ops.attention_tail(
             t1, t2, w['v'].reshape(-1), contexts, 0.0, False, self._seed,
             0)
         return mem0, out0, pooled.to(contexts.dtype)
 
-    def _setup(self, bufs, w, mem0, out0, pooled):
+    def _setup(self, bufs, w, mem0, out0, att, contexts):
         B, W, T, K, H, D, E = bufs.dims
-        bufs.pool.copy_(pooled.repeat_interleave(W, dim=0))
         emb0 = w['emb'][0]
-        for xh in bufs.xh:
-            xh[:, :D] = bufs.pool
+        if self.inloop:
+            # beam_attend fills the context columns every step
+            bufs.ctx.copy_(contexts)
+            bufs.l1.copy_(att)
+        else:
+            bufs.pool.copy_(att.repeat_interleave(W, dim=0))
+            for xh in bufs.xh:
+                xh[:, :D] = bufs.pool
+            bufs.expd[:, H:H + D] = bufs.pool
         bufs.xh[0][:, D:D + E] = emb0
         bufs.xh[0][:, D + E:] = out0.repeat_interleave(W, dim=0)
-        bufs.expd[:, H:H + D] = bufs.pool
         bufs.expd[:, H + D:] = emb0
         bufs.mem[0].copy_(mem0.repeat_interleave(W, dim=0))
         bufs.word[0].zero_()
@@ -205,6 +256,10 @@ class FusedBeamDecoder(object):
         B, W, T, K, H, D, E = bufs.dims
         cur, nxt = t % 2, (t + 1) % 2
         xh, mem, ids = bufs.xh[cur], bufs.mem[cur], bufs.word[cur]
+        if self.inloop:
+            # reads h from xh's state columns, writes pool and xh[:, :D]
+            ops.beam_attend(bufs.ctx, bufs.l1, w['wb'], xh, bufs.pool,
+                            bufs.alpha)
         if hip:
             from sat_amd import _C
             # the existing expand epilogues write the whole decode-input
@@ -220,14 +275,22 @@ class FusedBeamDecoder(object):
                 h_new, c_new = _C.lstm_pointwise_fwd(gates, mem, 1.0)
                 _C.expand_fuse(h_new, bufs.pool, w['emb'], ids, self._seed,
                                bufs.expd, self._empty, 0.0, 0.0, 0)
-            hid = _C.dense_fwd(bufs.expd, w['wd1'], w['bd1'], 1)
-            logits = _C.dense_fwd(hid, w['wd2'], w['bd2'], 0)
+            if self.dec1:
+                logits = _C.dense_fwd(bufs.expd, w['wd'], w['bd'], 0)
+            else:
+                hid = _C.dense_fwd(bufs.expd, w['wd1'], w['bd1'], 1)
+                logits = _C.dense_fwd(hid, w['wd2'], w['bd2'], 0)
         else:
             h_new, c_new = F.lstm_cell(xh[:, :D + E], xh[:, D + E:], mem,
                                        w['wl'], w['bl'])
             bufs.expd[:, :H] = h_new
-            hid = F.dense(bufs.expd, w['wd1'], w['bd1'], 'tanh')
-            logits = F.dense(hid, w['wd2'], w['bd2'], None)
+            if self.inloop:
+                bufs.expd[:, H:H + D] = bufs.pool
+            if self.dec1:
+                logits = F.dense(bufs.expd, w['wd'], w['bd'], None)
+            else:
+                hid = F.dense(bufs.expd, w['wd1'], w['bd1'], 'tanh')
+                logits = F.dense(hid, w['wd2'], w['bd2'], None)
         ops.softmax_topk(logits, K, out=(bufs.top_p, bufs.top_w))
         ops.beam_advance(bufs.state[cur], bufs.state[nxt], bufs.top_p,
                          bufs.top_w, period, c_new, h_new, w['emb'],
@@ -252,23 +315,31 @@ class FusedBeamDecoder(object):
                            word=bufs.word[nxt].reshape(B, W).clone(),
                            score=bufs.state[nxt][0].clone(),
                            c_scores=bufs.state[nxt][3].clone())
+                if self.inloop:
+                    rec['alpha'] = bufs.alpha.clone()
                 trace.append(rec)
 
     # ---- public ----
 
     @torch.no_grad()
     def search(self, contexts, period_id, beam_size, graph=True,
-               return_trace=False):
+               return_trace=False, mode=None):
         """contexts [B,L,D] -> per image a list of CaptionData (best
         first), as BaseModel.beam_search_device returns it.  With
         return_trace also a per-step list of dicts: the state fed to the
         step (last_word, memory, output, scores_in), the top_p / top_w it
-        produced and the selected (parent, word, score); a traced search
-        runs eagerly."""
-        mode = self.mode(contexts.is_cuda, contexts.dtype, beam_size)
+        produced, the selected (parent, word, score) and, with the
+        in-loop attention, its alpha [B*W,L]; a traced search runs
+        eagerly.  mode='twin' or 'hip' runs that form without asking
+        mode() (the CPU twin of the in-loop attention is offered this way
+        only)."""
         if mode is None:
-            raise ValueError('FusedBeamDecoder does not cover this '
-                             'configuration')
+            mode = self.mode(contexts.is_cuda, contexts.dtype, beam_size)
+            if mode is None:
+                raise ValueError('FusedBeamDecoder does not cover this '
+                                 'configuration')
+        elif mode not in ('twin', 'hip'):
+            raise ValueError("mode must be 'twin', 'hip' or None")
         hip = mode == 'hip'
         cfg = self.cfg
         B, L, D = contexts.shape
@@ -276,7 +347,7 @@ class FusedBeamDecoder(object):
         H, E = cfg.num_lstm_units, cfg.dim_embedding
         contexts = contexts.contiguous()
         w = self.weights(contexts.dtype)
-        mem0, out0, pooled = self._per_image(w, contexts)
+        mem0, out0, att = self._per_image(w, contexts)
 
         key = (B, W, T)
         trace = [] if return_trace else None
@@ -284,12 +355,13 @@ class FusedBeamDecoder(object):
         bufs = self._bufs.get(key) if graphed else None
         if bufs is None:
             bufs = _Buffers(B, W, T, K, H, D, E, contexts.dtype,
-                            contexts.device)
+                            contexts.device, L if self.inloop else 0,
+                            return_trace)
         period = int(period_id)
         if graphed and key not in self._graphs \
                 and len(self._graphs) < self.MAX_GRAPHS:
-            self._capture(key, bufs, w, period, mem0, out0, pooled)
-        self._setup(bufs, w, mem0, out0, pooled)
+            self._capture(key, bufs, w, period, mem0, out0, att, contexts)
+        self._setup(bufs, w, mem0, out0, att, contexts)
         g = self._graphs.get(key) if graphed else None
         if g is not None and g[1] == period:
             g[0].replay()
@@ -298,10 +370,10 @@ class FusedBeamDecoder(object):
         results = self._readout(bufs)
         return (results, trace) if return_trace else results
 
-    def _capture(self, key, bufs, w, period, mem0, out0, pooled):
+    def _capture(self, key, bufs, w, period, mem0, out0, att, contexts):
         """Warm the launches up on a side stream, then capture the T steps
         on one stream as one linear chain."""
-        self._setup(bufs, w, mem0, out0, pooled)
+        self._setup(bufs, w, mem0, out0, att, contexts)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):

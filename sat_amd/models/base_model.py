@@ -356,9 +356,13 @@ class BaseModel(object):
         """Beam search through sat_amd.beam.FusedBeamDecoder: per-image
         work once, the T steps as fused kernels in one captured graph
         (CPU: the same structure through the op layer's PyTorch twins).
-        Same hypothesis semantics and result structure as
-        beam_search_device, which also serves every configuration the
-        engine does not cover."""
+        Covers the 1- and 2-layer decode MLP and, on the GPU, the 1- and
+        2-layer attention: the 2-layer attention is hoisted out of the
+        loop, the 1-layer one runs inside it as the beam-shared
+        `beam_attend` kernel.  Same hypothesis semantics and result
+        structure as beam_search_device, which also serves every
+        configuration the engine does not cover (on the CPU that includes
+        the 1-layer attention)."""
         if self._fused_beam_mode() is None:
             return self.beam_search_device(image_files, vocabulary)
         self.model.eval()

@@ -132,3 +132,12 @@ def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
         from . import hip
         return hip.beam_advance(*args)
     return F.beam_advance(*args)
+
+
+def beam_attend(contexts, l1, wb, xh, pool, alpha=None):
+    """1-layer attention of one beam-search step for all B*W rows, written
+    in place (functional.beam_attend documents the contract)."""
+    if _use_hip(contexts):
+        from . import hip
+        return hip.beam_attend(contexts, l1, wb, xh, pool, alpha)
+    return F.beam_attend(contexts, l1, wb, xh, pool, alpha)

@@ -4,10 +4,13 @@
 //                  without writing the [R,V] probabilities anywhere
 //   beam_advance   everything beam search does between two decoder steps,
 //                  plus the next step's inputs, in one launch
+//   beam_attend    1-layer attention of one decoder step for all beams:
+//                  logits, softmax over locations and the pooled context,
+//                  each image's contexts read once for its W beams
 //
-// Both order their selections by (value descending, position ascending):
-// random bf16 logits tie often, and torch.topk promises no order among
-// ties, so the tie rule is part of the contract here.
+// The first two order their selections by (value descending, position
+// ascending): random bf16 logits tie often, and torch.topk promises no
+// order among ties, so the tie rule is part of the contract here.
 #include "common.h"
 
 #include <climits>
@@ -352,6 +355,287 @@ void check_rows(const at::Tensor& t, int64_t rows, int64_t cols,
                 " must be 16-byte aligned");
 }
 
+// ---------------------------------------------------------------------
+// beam_attend: grid (B, S), block (b, s) serves the W beams of image b and
+// the s-th slice of the D/8 column vectors.  Row n = b*W + w.
+//
+//   logit[n,l]  = l1[b,l] + sum_k h[n,k] * wb[l,k]     fp32
+//   alpha[n,:]  = softmax_l(logit[n,:])                fp32, max-subtracted
+//   pooled[n,d] = sum_l alpha[n,l] * ctx[b,l,d]        fp32, one rounding
+//
+// Phase 1 stages the image's W rows of h in LDS.  Phase 2: 8 lanes per
+// location (8 locations per wave, 32 per block and pass) walk wb[l,:] in
+// 16-byte loads against the W staged rows with the 2-element bf16 dot
+// instruction (fp32 accumulator) and meet in a 3-level xor tree.
+// Phase 3: one wave per row does the softmax in LDS.  Phase 4: thread
+// (tl, tc) keeps W x 8 fp32 accumulators for column vector tc over the
+// locations tl, tl + LG, ...: a context vector is loaded once and used by
+// all W beams.  The LG partial sums meet through LDS in index order.
+// Every block repeats phases 1-3 (cheap next to phase 4 at small B·S, and
+// what lets S > 1 spread one image over several CUs); block s == 0 writes
+// alpha.  No atomics and no order that depends on timing: two launches on
+// the same inputs give the same bits.
+//
+// The kernel reads columns [D+E, D+E+H) of xh (h, where beam_advance and
+// the engine's setup put it) and writes columns [0, D) of the same rows.
+// The two ranges are disjoint and no block reads what another writes, so
+// unlike beam_advance, whose slots read their PARENTS' rows and would race
+// an in-place reorder, it needs no second buffer.
+// ---------------------------------------------------------------------
+
+constexpr int ATT_THREADS = 256;
+constexpr int ATT_WAVES = ATT_THREADS / 64;
+constexpr int ATT_MAX_L = 1024;     // W*L fp32 logits: 32 KiB at W = 8
+constexpr int ATT_MAX_H = 2048;     // W*H bf16 staged h: 32 KiB at W = 8
+constexpr int ATT_GRID = 256;       // one block per CU
+constexpr int ATT_UNROLL = 8;       // 16-byte loads in flight per lane
+constexpr int ATT_MIN_VEC = 16;     // profiles/beam_attend_perf_log.md
+
+// beams whose partial sums cross the waves through LDS in one pass
+template <int W> struct AttChunk { static constexpr int n = W < 4 ? W : 4; };
+
+// bytes of the region shared by the staged h (phases 1-2) and the
+// partial sums (phase 4)
+static inline size_t att_union_bytes(int W, int H) {
+    const size_t h_bytes = (size_t)W * H * sizeof(bf16);
+    const size_t part = (size_t)ATT_THREADS * (W < 4 ? W : 4) * 8
+        * sizeof(float);
+    return h_bytes > part ? h_bytes : part;
+}
+
+// S, the blocks per image: the largest power of two that keeps B*S within
+// ATT_GRID blocks and leaves a block at least ATT_MIN_VEC column vectors
+static inline int att_split(int B, int nvec) {
+    int S = 1;
+    while (B * S * 2 <= ATT_GRID && nvec / (S * 2) >= ATT_MIN_VEC) S *= 2;
+    return S;
+}
+
+__device__ __forceinline__ float xor_sum(float v, int from) {
+    for (int off = from; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ int cdiv_dev(int a, int b) {
+    return a > 0 ? (a + b - 1) / b : 0;
+}
+
+// acc + sum of 8 bf16 products, fp32: four 2-element bf16 dot instructions
+__device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b, float acc) {
+    acc = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_shufflevector(a, a, 0, 1),
+        __builtin_shufflevector(b, b, 0, 1), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_shufflevector(a, a, 2, 3),
+        __builtin_shufflevector(b, b, 2, 3), acc, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_shufflevector(a, a, 4, 5),
+        __builtin_shufflevector(b, b, 4, 5), acc, false);
+    return __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_shufflevector(a, a, 6, 7),
+        __builtin_shufflevector(b, b, 6, 7), acc, false);
+}
+
+// pass `it` of a wave's logits phase: location l = l_first + p * 32 and
+// the vectors (c * ATT_UNROLL + u) * 8 + sub of wb[l,:], with
+// (p, c) = divmod(it, nchunk); what lies past L or H loads as zero
+__device__ __forceinline__ void att_load_wb(bf16x8 (&buf)[ATT_UNROLL],
+                                            const bf16* __restrict__ wb,
+                                            int it, int nchunk, int l_first,
+                                            int sub, int L, int H) {
+    const int p = it / nchunk, c = it - p * nchunk;
+    const int l = l_first + p * ATT_WAVES * 8;
+    const bf16* wr = wb + (int64_t)l * H;
+#pragma unroll
+    for (int u = 0; u < ATT_UNROLL; ++u) {
+        const int jv = (c * ATT_UNROLL + u) * 8 + sub;
+        bf16x8 v = {};
+        if (l < L && jv < H / 8) v = *(const bf16x8*)(wr + jv * 8);
+        buf[u] = v;
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(ATT_THREADS)
+void beam_attend_kernel(const bf16* __restrict__ ctx,     // [B,L,D]
+                        const float* __restrict__ l1,     // [B,L]
+                        const bf16* __restrict__ wb,      // [L,H]
+                        bf16* xh,                         // [B*W,D+E+H]
+                        bf16* __restrict__ pool,          // [B*W,D]
+                        float* __restrict__ alpha,        // [B*W,L] or null
+                        int L, int D, int E, int H,
+                        int cv,        // column vectors per block
+                        int CW,        // power of two, min(cv, 256) <= CW
+                        int union_bytes) {
+    constexpr int WC = AttChunk<W>::n;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int nvec = D / 8, v0 = blockIdx.y * cv;
+    const int NC = (nvec - v0 < cv) ? nvec - v0 : cv;
+    if (NC <= 0) return;                // whole block, before any barrier
+    const int XS = D + E + H;
+    const int64_t row0 = (int64_t)b * W;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char att_lds[];
+    bf16* s_h = (bf16*)att_lds;                         // [W,H]
+    float* s_part = (float*)att_lds;                    // [LG,WC,CW*8]
+    float* s_a = (float*)(att_lds + union_bytes);       // [W,L]
+
+    // ---- 1. h rows of this image ----
+    const int H8 = H / 8;
+    for (int idx = tid; idx < W * H8; idx += ATT_THREADS) {
+        const int w = idx / H8, q = idx - w * H8;
+        *(uint4*)(s_h + w * H + q * 8) =
+            *(const uint4*)(xh + (row0 + w) * XS + D + E + q * 8);
+    }
+    __syncthreads();
+
+    // ---- 2. logits: 8 lanes per location ----
+    // A pass is 8 locations per wave and ATT_UNROLL*8 vectors of H per
+    // location: its loads are issued together, and the next pass's before
+    // this pass's arithmetic, so a wave waits for memory once per pass and
+    // not once per load.
+    {
+        const int sub = lane & 7, grp = lane >> 3;
+        const int nchunk = cdiv_dev(H8, ATT_UNROLL * 8);
+        const int npass = cdiv_dev(L - wave * 8, ATT_WAVES * 8) * nchunk;
+        bf16x8 cur[ATT_UNROLL], nxt[ATT_UNROLL] = {};
+        att_load_wb(cur, wb, 0, nchunk, wave * 8 + grp, sub, L, H);
+        float acc[W];
+        for (int it = 0; it < npass; ++it) {
+            if (it + 1 < npass)
+                att_load_wb(nxt, wb, it + 1, nchunk, wave * 8 + grp, sub,
+                            L, H);
+            const int p = it / nchunk, c = it - p * nchunk;
+            if (c == 0) {
+#pragma unroll
+                for (int w = 0; w < W; ++w) acc[w] = 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < ATT_UNROLL; ++u) {
+                const int jv = (c * ATT_UNROLL + u) * 8 + sub;
+                if (jv < H8) {
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        acc[w] = dot8(*(const bf16x8*)(s_h + w * H + jv * 8),
+                                      cur[u], acc[w]);
+                }
+            }
+            if (c == nchunk - 1) {          // wave-uniform
+                const int l = wave * 8 + p * ATT_WAVES * 8 + grp;
+#pragma unroll
+                for (int w = 0; w < W; ++w) acc[w] = xor_sum(acc[w], 4);
+                if (l < L && sub == 0) {
+                    const float base = l1[(int64_t)b * L + l];
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        s_a[w * L + l] = base + acc[w];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < ATT_UNROLL; ++u) cur[u] = nxt[u];
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. softmax, one wave per row (xor trees: every lane ends with
+    // the same bits) ----
+    for (int w = wave; w < W; w += ATT_WAVES) {
+        float* row = s_a + w * L;
+        float m = -INFINITY;
+        for (int l = lane; l < L; l += 64) m = fmaxf(m, row[l]);
+        for (int off = 32; off > 0; off >>= 1)
+            m = fmaxf(m, __shfl_xor(m, off, 64));
+        float s = 0.f;
+        for (int l = lane; l < L; l += 64) {
+            const float e = __expf(row[l] - m);
+            row[l] = e;
+            s += e;
+        }
+        s = xor_sum(s, 32);
+        const float inv = 1.0f / s;
+        for (int l = lane; l < L; l += 64) {
+            const float a = row[l] * inv;
+            row[l] = a;
+            if (alpha != nullptr && blockIdx.y == 0)
+                alpha[(row0 + w) * L + l] = a;
+        }
+    }
+    __syncthreads();    // s_a complete; s_h is dead from here (s_part)
+
+    // ---- 4. pooled columns [v0, v0 + NC) ----
+    const int LG = ATT_THREADS / CW;
+    const int tc = tid & (CW - 1), tl = tid / CW;
+    const bf16* cb = ctx + (int64_t)b * L * D;
+    for (int c0 = 0; c0 < NC; c0 += CW) {       // once unless cv > 256
+        const int c = c0 + tc;
+        float acc[W][8];
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[w][e] = 0.f;
+        if (c < NC) {
+            const bf16* cp = cb + (int64_t)(v0 + c) * 8;
+#pragma unroll 4
+            for (int l = tl; l < L; l += LG) {
+                const bf16x8 x = *(const bf16x8*)(cp + (int64_t)l * D);
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const float a = s_a[w * L + l];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        acc[w][e] += a * bf2f(x[e]);
+                }
+            }
+        }
+#pragma unroll
+        for (int w0 = 0; w0 < W; w0 += WC) {
+            __syncthreads();            // s_part (or s_h) no longer read
+#pragma unroll
+            for (int wi = 0; wi < WC; ++wi) {
+                if (w0 + wi < W) {
+                    float* dst = s_part + ((tl * WC + wi) * CW + tc) * 8;
+                    *(floatx4*)dst = floatx4{acc[w0 + wi][0],
+                                             acc[w0 + wi][1],
+                                             acc[w0 + wi][2],
+                                             acc[w0 + wi][3]};
+                    *(floatx4*)(dst + 4) = floatx4{acc[w0 + wi][4],
+                                                   acc[w0 + wi][5],
+                                                   acc[w0 + wi][6],
+                                                   acc[w0 + wi][7]};
+                }
+            }
+            __syncthreads();
+            // (beam, column vector) per thread: the LG partial sums in
+            // index order, one rounding, the same 16 bytes to pool and xh
+            for (int idx = tid; idx < WC * CW; idx += ATT_THREADS) {
+                const int wi = idx / CW, ci = idx - wi * CW;
+                const int w = w0 + wi;
+                if (w >= W || c0 + ci >= NC) continue;
+                float s[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s[e] = 0.f;
+                for (int g = 0; g < LG; ++g) {
+                    const float* src = s_part + ((g * WC + wi) * CW + ci) * 8;
+                    const floatx4 lo = *(const floatx4*)src;
+                    const floatx4 hi = *(const floatx4*)(src + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        s[e] += lo[e];
+                        s[4 + e] += hi[e];
+                    }
+                }
+                bf16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = f2bf(s[e]);
+                const int64_t col = (int64_t)(v0 + c0 + ci) * 8;
+                *(bf16x8*)(pool + (row0 + w) * D + col) = o;
+                *(bf16x8*)(xh + (row0 + w) * XS + col) = o;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // p [R,K] fp32 and idx [R,K] int64 are written in place
@@ -458,5 +742,78 @@ void beam_advance(std::vector<at::Tensor> state_in,
                        (int64_t*)last_word.data_ptr(),
                        (int64_t*)parent.data_ptr(), (int)W, (int)K, (int)T,
                        (int)H, (int)D, (int)E, (int)V, period);
+    HIP_OK(hipGetLastError());
+}
+
+// contexts [B,L,D], l1 [B,L] fp32, wb [L,H], xh [B*W,D+E+H]: pooled
+// contexts into pool [B*W,D] and xh[:, :D] (the same bits), softmax
+// weights into alpha [B*W,L] fp32 unless it is empty.  split = S, the
+// number of blocks per image (0: chosen here).
+void beam_attend(at::Tensor contexts, at::Tensor l1, at::Tensor wb,
+                 at::Tensor xh, at::Tensor pool, at::Tensor alpha,
+                 int64_t split) {
+    CHECK_GPU(contexts); CHECK_CONTIG(contexts); CHECK_BF16(contexts);
+    CHECK_GPU(l1); CHECK_CONTIG(l1); CHECK_F32(l1);
+    TORCH_CHECK(contexts.dim() == 3 && wb.dim() == 2 && xh.dim() == 2,
+                "beam_attend: contexts [B,L,D], wb [L,H], xh [B*W,D+E+H]");
+    const int64_t B = contexts.size(0), L = contexts.size(1),
+                  D = contexts.size(2), H = wb.size(1);
+    TORCH_CHECK(B >= 1 && xh.size(0) % B == 0,
+                "beam_attend: xh rows must be B*W");
+    const int64_t W = xh.size(0) / B, E = xh.size(1) - D - H;
+    TORCH_CHECK(W >= 1 && W <= MAX_BEAM, "beam_attend: 1 <= W <= 8");
+    TORCH_CHECK(L >= 1 && L <= ATT_MAX_L, "beam_attend: 1 <= L <= ",
+                ATT_MAX_L);
+    TORCH_CHECK(H >= 8 && H <= ATT_MAX_H && H % 8 == 0 && D >= 8
+                && D % 8 == 0 && E >= 0 && E % 8 == 0,
+                "beam_attend: D, E, H multiples of 8, 8 <= H <= ",
+                ATT_MAX_H);
+    TORCH_CHECK(((uintptr_t)contexts.data_ptr() & 15) == 0,
+                "contexts must be 16-byte aligned");
+    TORCH_CHECK(l1.dim() == 2 && l1.size(0) == B && l1.size(1) == L,
+                "l1 must be [B,L]");
+    check_rows(wb, L, H, "wb");
+    check_rows(xh, B * W, D + E + H, "xh");
+    check_rows(pool, B * W, D, "pool");
+    TORCH_CHECK(B * L * D < INT_MAX && B * W * (D + E + H) < INT_MAX
+                && B * W * L < INT_MAX && L * H < INT_MAX,
+                "beam_attend: batch out of range");
+    float* alpha_ptr = nullptr;
+    if (alpha.defined() && alpha.numel() > 0) {
+        CHECK_GPU(alpha); CHECK_CONTIG(alpha); CHECK_F32(alpha);
+        TORCH_CHECK(alpha.dim() == 2 && alpha.size(0) == B * W
+                    && alpha.size(1) == L, "alpha must be [B*W,L]");
+        alpha_ptr = (float*)alpha.data_ptr();
+    }
+
+    const int nvec = (int)(D / 8);
+    TORCH_CHECK(split >= 0 && split <= nvec,
+                "beam_attend: 0 <= split <= D / 8");
+    int S = (int)split;
+    if (S == 0) S = att_split((int)B, nvec);
+    const int cv = cdiv(nvec, S);
+    int CW = 1;
+    while (CW < cv && CW < ATT_THREADS) CW <<= 1;
+    const size_t ub = att_union_bytes((int)W, (int)H);
+    const size_t lds = ub + (size_t)W * L * sizeof(float);
+
+    hipStream_t stream = at::cuda::getCurrentCUDAStream();
+#define LAUNCH_ATTEND(WW) \
+    case WW: \
+        hipLaunchKernelGGL(beam_attend_kernel<WW>, \
+                           dim3((unsigned)B, (unsigned)S), \
+                           dim3(ATT_THREADS), lds, stream, \
+                           (const bf16*)contexts.data_ptr(), \
+                           (const float*)l1.data_ptr(), \
+                           (const bf16*)wb.data_ptr(), \
+                           (bf16*)xh.data_ptr(), (bf16*)pool.data_ptr(), \
+                           alpha_ptr, (int)L, (int)D, (int)E, (int)H, cv, \
+                           CW, (int)ub); \
+        break;
+    switch (W) {
+        LAUNCH_ATTEND(1) LAUNCH_ATTEND(2) LAUNCH_ATTEND(3) LAUNCH_ATTEND(4)
+        LAUNCH_ATTEND(5) LAUNCH_ATTEND(6) LAUNCH_ATTEND(7) LAUNCH_ATTEND(8)
+    }
+#undef LAUNCH_ATTEND
     HIP_OK(hipGetLastError());
 }

@@ -178,6 +178,9 @@ void beam_advance(std::vector<at::Tensor> state_in,
                   at::Tensor h_new, at::Tensor table, at::Tensor mem_next,
                   at::Tensor xh_next, at::Tensor exp_next,
                   at::Tensor last_word, at::Tensor parent);
+void beam_attend(at::Tensor contexts, at::Tensor l1, at::Tensor wb,
+                 at::Tensor xh, at::Tensor pool, at::Tensor alpha,
+                 int64_t split);
 at::Tensor resize_normalize_u8(at::Tensor packed, at::Tensor desc,
                                at::Tensor tables, at::Tensor mean,
                                int64_t OH, int64_t OW, bool bf16_out);
@@ -276,6 +279,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("beam_advance", &beam_advance,
           "beam bookkeeping of one step + the next step's LSTM / decode "
           "input rows in one launch");
+    m.def("beam_attend", &beam_attend,
+          "1-layer attention of one decoder step for all beams: logits, "
+          "softmax over L and pooled contexts into pool and xh[:, :D]",
+          py::arg("contexts"), py::arg("l1"), py::arg("wb"), py::arg("xh"),
+          py::arg("pool"), py::arg("alpha"), py::arg("split") = 0);
     m.def("resize_normalize_u8", &resize_normalize_u8,
           "packed uint8 HWC images -> [N,3,OH,OW] channels_last: Pillow's "
           "8-bit bilinear resize, minus the mean, as bf16 or fp32");

@@ -174,6 +174,38 @@ def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
     parent.copy_(sel_parent.reshape(parent.shape))
 
 
+def beam_attend(contexts, l1, wb, xh, pool, alpha=None):
+    """1-layer attention (Decoder.attend with num_attend_layers == 1) of
+    one beam-search step, for all beams at once.  Row n = b*W + w is beam
+    w of image b; W = xh.shape[0] // B.
+
+    contexts [B,L,D] (not repeated per beam); l1 [B,L] fp32, the
+    per-image constant contexts · att_fc_a.weight; wb [L,H] =
+    att_fc_b.weight; xh [B*W, D+E+H], the step's LSTM-input rows, whose
+    last H columns hold h.
+
+        logit[n,l]  = l1[b,l] + sum_k h[n,k] * wb[l,k]
+        alpha[n,:]  = softmax over l of logit[n,:]
+        pooled[n,d] = sum_l alpha[n,l] * contexts[b,l,d]
+
+    all in fp32, pooled rounded once to pool's dtype.  Written in place:
+    pool [B*W,D] and xh[:, :D] receive the same values; alpha [B*W,L]
+    fp32 receives the weights unless it is None or empty.  The other
+    columns of xh are read (h) or left alone."""
+    B, L, D = contexts.shape
+    W = xh.shape[0] // B
+    H = wb.shape[1]
+    h = xh[:, xh.shape[1] - H:].float()
+    logits = l1.float().repeat_interleave(W, dim=0) \
+        + h.matmul(wb.float().t())
+    a, pooled = attention_pool(
+        contexts.float().repeat_interleave(W, dim=0), logits)
+    pool.copy_(pooled)
+    xh[:, :D] = pool
+    if alpha is not None and alpha.numel() > 0:
+        alpha.copy_(a)
+
+
 def _resample_u8(src, table, out_size, ksize, dim):
     """One pass of Pillow's 8-bit resample along `dim` of src [H,W,3]
     uint8.  `table` is an axis table of ImagePrep: first source index and

@@ -10,6 +10,7 @@ sat_amd/ops/csrc/*.hip, gfx950-only) provides:
   ce_fwd / ce_bwd                 fused masked softmax cross-entropy
   grad_sq_norm / adam_step        fused global-norm clip + Adam
   softmax_topk / beam_advance     beam-search inference (sat_amd/beam.py)
+  beam_attend                     its in-loop 1-layer attention, beam-shared
   resize_normalize_u8             Pillow-exact resize + mean + cast of packed
                                   uint8 images (sat_amd/data/pipeline.py)
 
@@ -52,6 +53,13 @@ def _empty(device):
     key = str(device)
     if key not in _EMPTY:
         _EMPTY[key] = torch.empty(0, device=device, dtype=torch.bfloat16)
+    return _EMPTY[key]
+
+
+def _empty_f32(device):
+    key = ('f32', str(device))
+    if key not in _EMPTY:
+        _EMPTY[key] = torch.empty(0, device=device, dtype=torch.float32)
     return _EMPTY[key]
 
 
@@ -237,6 +245,15 @@ def beam_advance(state_in, state_out, top_p, top_w, period, mem_new, h_new,
                     int(period), mem_new, h_new, table, mem_next, xh_next,
                     exp_next if exp_next is not None else _empty(table.device),
                     last_word, parent)
+
+
+def beam_attend(contexts, l1, wb, xh, pool, alpha=None, split=0):
+    """1-layer attention of one decoder step for all beams, in place into
+    pool and xh[:, :D] (and alpha when given); split = blocks per image,
+    0 for the kernel's own choice."""
+    _C.beam_attend(contexts, l1, wb, xh, pool,
+                   alpha if alpha is not None
+                   else _empty_f32(contexts.device), int(split))
 
 
 # ---- input pipeline (no autograd; called by sat_amd.data.pipeline) ----
